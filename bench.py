@@ -3,6 +3,15 @@ on ogbn-products-shaped mini-batches, fanout [15,10], batch 1024 (BASELINE.json)
 
     python bench.py [--gpus N] [--steps K] [--warmup W]   (N > 1: starts N ranks itself)
     torchrun --nproc-per-node N bench.py --gpus N ...   (one process per GPU)
+    python bench.py ... --full                          (+ every secondary measurement below)
+    python bench.py ... --dump-outputs DIR              (the last timed step's results as .npy)
+
+A plain run sets up, warms up, times the K steps and prints the result line;
+everything under "Also reported" runs only with --full (those fields are null
+in a plain run's line).  --dump-outputs: the last timed step restarts from the
+seeded initial weights and optimizer state, and its loss, seed-row logits and
+updated parameters are written -- the same values every run, up to the
+rounding of one step's atomic adds.
 
 Workload (config.workload = "products-[15,10]-bs1024"): synthetic graph with
 ogbn-products' published sizes (N=2,449,029, 123.7 M directed entries, F=100,
@@ -17,7 +26,7 @@ all-reduce (N>1) and Adam.  Aggregated edges per step = num_layers x E_batch
 (every layer aggregates all E edges of the block, sage.py:33-34).
 value = sum over ranks of edges / max-over-ranks wall time.
 
-Also reported: epoch_time_s — one full pass over this rank's train seeds
+Also reported (--full): epoch_time_s — one full pass over this rank's train seeds
 INCLUDING GPU sampling + feature gather (193 batches at N=1); graph mode: the
 sync-free loader (no host wait per batch) with the fused x[n_id] gather
 (epoch_mode), beside it the sync-free loader with the loader's row copy and
@@ -62,6 +71,19 @@ def parse():
                     help="model.py's `module`: SAGE (sage.py) or SimpleGCN (convolution.py)")
     ap.add_argument("--dtype", default="f32", choices=["f32", "bf16"],
                     help="model / feature storage dtype (bf16: bf16 feature rows and one-part bf16 weight images, fp32 accumulation)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements: per-kernel timing and the roofline of "
+                         "the dominant kernel, the all-reduce timing (N > 1), the eager reference "
+                         "loop, the epochs over the loader and the CPU baseline (each can be switched "
+                         "off with its --no-* option); without it the run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (its loss, "
+                         "the seed rows' logits, every parameter after its optimizer step) as "
+                         "DIR/<name>.npy (float32).  With this option the last timed step starts again "
+                         "from the seeded initial weights and a fresh optimizer state (a few device "
+                         "copies inside the timed region), so its results depend on the seeded inputs "
+                         "alone and two builds run with the same arguments can be compared output for "
+                         "output")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-epoch", action="store_true")
     ap.add_argument("--no-eager-ref", action="store_true",
@@ -121,7 +143,39 @@ def train_step(model, opt, reducer, b):
     loss.backward()
     reducer()
     opt.step()
-    return loss
+    return loss, out.detach()
+
+
+class SeededState:
+    """The parameters and optimizer state of (model, optimizer) pairs as they
+    are before the first training step, to put back in place later (the same
+    tensors: a captured step keeps their addresses)."""
+
+    def __init__(self, pairs):
+        self.pairs = pairs
+        self.params = [[p.detach().clone() for p in m.parameters()] for m, _ in pairs]
+        self.state = [{k: {n: t.clone() for n, t in st.items() if torch.is_tensor(t)}
+                       for k, st in o.state.items()} for _, o in pairs]
+
+    @torch.no_grad()
+    def restore(self):
+        for (m, o), ps, sts in zip(self.pairs, self.params, self.state):
+            for p, v in zip(m.parameters(), ps):
+                p.copy_(v)
+            for k, st in o.state.items():
+                old = sts.get(k, {})
+                for n, t in st.items():
+                    if torch.is_tensor(t):  # (state born after the snapshot: a fresh optimizer's zeros)
+                        t.copy_(old[n]) if n in old else t.zero_()
+
+
+def dump_outputs(path, named):
+    """--dump-outputs: every (name, tensor) as path/<name>.npy in float32 (the
+    step's results are a few hundred KB: nothing is sampled)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in named:
+        np.save(os.path.join(path, name + ".npy"), t.detach().to("cpu", torch.float32).numpy())
 
 
 def _cpu_model() -> str:
@@ -461,15 +515,19 @@ def main():
         raise SystemExit("bench.py: --gpus must be >= 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
+    if not args.full:  # a plain run: the timed steps only
+        args.no_eager_ref = args.no_epoch = args.no_cpu_baseline = True
     import torch.distributed as dist
 
     import ngnn
     from ngnn import _timing
-    from ngnn.distributed import GradAllReduce, init
+    from ngnn.distributed import GradAllReduce, env_world, init
     from ngnn.loader import NeighborLoader, sample_block, synthetic_graph
 
+    # before the rendezvous: a rank without a GPU of its own must say so and
+    # exit, not fail in set_device and leave the other ranks waiting for it
+    check_world(args.gpus, env_world()[1])
     rank, world, local = init()
-    check_world(args.gpus, world)
     # (one GPU per rank; modulo only matters when rehearsing N ranks on fewer GPUs)
     dev = torch.device("cuda", local % max(1, torch.cuda.device_count()))
     torch.cuda.set_device(dev)
@@ -535,7 +593,7 @@ def main():
         gstep.capture(b0.x, b0.edge_index, b0.yhn, b0.n_id, args.forget_rate)
 
         def run(b):
-            gstep(b.x, b.edge_index, b.yhn, b.n_id, args.forget_rate, b.batch_size)
+            return gstep(b.x, b.edge_index, b.yhn, b.n_id, args.forget_rate, b.batch_size)
     elif graph:
         # the whole step (CSR build .. Adam) as one captured HIP graph over a
         # static slot sized for any block of this fanout (ngnn/graphs.py)
@@ -546,11 +604,20 @@ def main():
         gstep.capture(batches[0].x, batches[0].edge_index, batches[0].y)
 
         def run(b):
-            gstep(b.x, b.edge_index, b.y, b.batch_size)
+            return gstep(b.x, b.edge_index, b.y, b.batch_size)
     else:
         def run(b):
-            train_step(model, opt, reducer, b)
+            return train_step(model, opt, reducer, b)
 
+    # --dump-outputs: the last timed step starts from the seeded weights and a
+    # fresh optimizer state again, so what it computes depends on the seeded
+    # inputs alone.  (The backward's scatter adds floats atomically, in an
+    # order that differs from run to run; one step keeps that to rounding,
+    # but training on amplifies it step by step -- after 220 steps two runs
+    # of one build were 2e-2 apart in the logits.)
+    seeded = None
+    if args.dump_outputs:
+        seeded = SeededState([(model, opt)] + ([(ct[0], ct[1])] if ct is not None else []))
     for i in range(args.warmup):
         run(batches[i % nb])
     barrier()
@@ -565,22 +632,40 @@ def main():
     # batches are timed in an eager pass right after the timed replays
     timer = new_timer() if not graph else _timing.KernelTimer(only=["-"])
     edges = 0
+    res = b = None
     t0 = time.perf_counter()
     with timer:
         for i in range(args.steps):
             b = batches[(args.warmup + i) % nb]
-            run(b)
+            if seeded is not None and i == args.steps - 1:
+                seeded.restore()  # (stream-ordered device copies: no wait)
+            res = run(b)
             edges += (2 if ct is not None else 1) * layers * b.edge_index.shape[1]
     t_issue = time.perf_counter() - t0  # host time to enqueue the K steps
     barrier()
     dt = time.perf_counter() - t0
-    if graph and args.timer != "none" and ct is None:
+    if args.dump_outputs and rank == 0 and res is not None:
+        # what the last timed step handed its caller, before anything below
+        # trains on: the loss(es), the seed rows' logits (the rows the loss
+        # reads; a captured step keeps them in its static output) and every
+        # parameter after the step's Adam update
+        if ct is not None:
+            named = list(zip(("loss_1", "loss_2", "pure_ratio_1", "pure_ratio_2"), res[:4]))
+            named = [(k, torch.as_tensor(v)) for k, v in named]
+        elif graph:
+            named = [("loss", res), ("logits", gstep.out[:b.batch_size])]
+        else:
+            named = [("loss", res[0]), ("logits", res[1][:b.batch_size])]
+        for tag, m in (("param", model),) + ((("param2", ct[0]),) if ct is not None else ()):
+            named += [(f"{tag}.{k}", p) for k, p in m.named_parameters()]
+        dump_outputs(args.dump_outputs, named)
+    if args.full and graph and args.timer != "none" and ct is None:
         timer = new_timer()
         with timer:
             for i in range(args.steps):
                 train_step(model, opt, reducer, batches[(args.warmup + i) % nb])
         barrier()
-    ar = allreduce_us(reducer, world)
+    ar = allreduce_us(reducer, world) if args.full else None
     t = torch.tensor([dt, float(edges)], dtype=torch.float64, device=dev)
     if world > 1:
         tmax = t.clone()
@@ -771,7 +856,7 @@ def main():
                       else f"aggregated edges/sec (GraphSAGE train step), {args.dataset} "
                            f"fanout=[{args.fanout}] bs={args.batch_size}",
             "value": round(edges / dt, 1), "unit": "edges/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup,
+            "steps": args.steps, "warmup": args.warmup, "full": args.full,
             "ms_per_step": round(1e3 * dt / args.steps, 4), "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": args.dtype,
             "data": f"synthetic (seeded Chung-Lu graph with {args.dataset} sizes; random features)",

@@ -7,6 +7,6 @@ O=gpurun_out/${TAG:-abl}; mkdir -p $O
 for v in head ${VARIANTS:-}; do
   if [ $v = head ]; then unset NGNN_LIB; else export NGNN_LIB=$PWD/ablib/$v.so; fi
   timeout -k 10 200 python3 tools/kbench_fwd.py > $O/kbench_$v.json 2>&1 || exit $?
-  timeout -k 10 200 python3 bench.py --no-cpu-baseline --no-epoch --gather ${GATHER:-loader} > $O/bench_$v.log 2>&1 || exit $?
+  timeout -k 10 200 python3 bench.py --full --no-cpu-baseline --no-epoch --gather ${GATHER:-loader} > $O/bench_$v.log 2>&1 || exit $?
 done
 echo done

@@ -1,5 +1,5 @@
 """Where an epoch's time goes, from a rocprofv3 --kernel-trace CSV of
-bench.py (whose last phase is the epoch over the loader).
+bench.py --full (whose last phase is the epoch over the loader).
 
 Takes the last --batches windows that start at a sampler launch (k_sb_init,
 one per batch) and reports, per window and in total: wall time, the busy
@@ -35,7 +35,7 @@ def main():
     ap.add_argument("--batches", type=int, default=193)
     ap.add_argument("--marker", default="k_sb_init")
     ap.add_argument("--skip-last", type=int, default=0,
-                    help="windows to leave out at the end (bench.py's second, fused-gather epoch)")
+                    help="windows to leave out at the end (bench.py --full's second, fused-gather epoch)")
     a = ap.parse_args()
     rows = list(csv.DictReader(open(a.trace)))
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))

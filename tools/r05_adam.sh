@@ -12,9 +12,9 @@ timeout -k 10 200 python tools/adam_micro.py > $O/micro.log 2>&1 || { tail -20 $
 tail -5 $O/micro.log
 A="--dataset computers --fanout 10,5 --batch-size 300 --hidden 512 --aggr max --no-cpu-baseline --no-epoch --no-eager-ref"
 for i in 1 2; do
-  timeout -k 10 300 python bench.py $A > $O/b_$i.log 2>&1 || exit 1
+  timeout -k 10 300 python bench.py --full $A > $O/b_$i.log 2>&1 || exit 1
   python3 -c "import json; print(json.loads(open('$O/b_$i.log').read().strip().splitlines()[-1])['ms_per_step'])"
 done
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python3 bench.py --steps 20 --warmup 5 --timer none $A > $O/prof.log 2>&1 || exit 1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python3 bench.py --full --steps 20 --warmup 5 --timer none $A > $O/prof.log 2>&1 || exit 1
 python3 tools/trace_step.py $O/prof/run_kernel_trace.csv --marker k_slot_load --skip 8 --steps 10 > $O/step.txt 2>&1
 grep -E "k_adam|step span" $O/step.txt

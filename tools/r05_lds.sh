@@ -10,5 +10,5 @@ tail -1 $O/pytest.log
 g="SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_WAIT_INST_LDS"
 timeout -s KILL 120 rocprofv3 --kernel-trace --pmc $g --kernel-include-regex "k_fwd2<" -d $O/s -o run --output-format csv -- python3 tools/fwd2_micro.py --stages main --reps 10 > $O/s.log 2>&1 || { tail -3 $O/s.log; exit 1; }
 for i in 1 2; do timeout -k 10 120 python3 tools/fwd2_micro.py --stages main,fused --reps 50 > $O/micro$i.log 2>&1 || exit 1; tail -2 $O/micro$i.log; done
-timeout -k 10 300 python bench.py --no-cpu-baseline --no-epoch --no-eager-ref > $O/bench.log 2>&1 || exit 1
+timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-epoch --no-eager-ref > $O/bench.log 2>&1 || exit 1
 tail -1 $O/bench.log | cut -c1-200

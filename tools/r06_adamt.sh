@@ -20,6 +20,6 @@ for r in csv.DictReader(open('$O/prof/run_kernel_stats.csv')):
     if 'adam' in r['Name']: print('   ', r['Name'][:40], r['Calls'], round(float(r['AverageNs'])/1e3,2), 'us')"
 NGNN_ADAM_WG_PER_CU=1 step micro_w1 120 python3 tools/adam_micro.py
 A="--dataset computers --fanout 10,5 --batch-size 300 --hidden 512 --aggr max"
-step bench_c1 300 python3 bench.py --no-cpu-baseline --no-eager-ref --no-epoch $A
-step bench_c2 300 python3 bench.py --no-cpu-baseline --no-eager-ref --no-epoch $A
+step bench_c1 300 python3 bench.py --full --no-cpu-baseline --no-eager-ref --no-epoch $A
+step bench_c2 300 python3 bench.py --full --no-cpu-baseline --no-eager-ref --no-epoch $A
 echo done

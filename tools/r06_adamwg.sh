@@ -15,6 +15,6 @@ step() {
 A="--dataset computers --fanout 10,5 --batch-size 300 --hidden 512 --aggr max"
 step pytest 500 python -u -m pytest tests/test_gpu_fused.py tests/test_gpu_configs.py tests/test_optim_gpu.py -q -x --timeout 200 --timeout-method thread
 for w in 2 4 3 8 2 4; do
-  NGNN_ADAM_WG_PER_CU=$w step bench_w$w 300 python3 bench.py --no-cpu-baseline --no-eager-ref --no-epoch $A
+  NGNN_ADAM_WG_PER_CU=$w step bench_w$w 300 python3 bench.py --full --no-cpu-baseline --no-eager-ref --no-epoch $A
 done
 echo done

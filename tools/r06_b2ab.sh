@@ -23,8 +23,8 @@ step prof_old 200 rocprofv3 --kernel-trace --stats -d $O/prof_old -o run --outpu
 grep -h "k_bwd2" $O/prof_old/run_kernel_stats.csv | cut -c1-160
 unset NGNN_LIB
 step pytest 300 python -u -m pytest tests/test_gpu_bwd2.py tests/test_gpu_fold.py -q -x --timeout 120 --timeout-method thread
-step bench_headline 400 python3 bench.py --no-cpu-baseline --no-eager-ref
-step prof_headline 400 rocprofv3 --kernel-trace --stats -d $O/prof_headline -o run --output-format csv -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-epoch --no-eager-ref --timer none
+step bench_headline 400 python3 bench.py --full --no-cpu-baseline --no-eager-ref
+step prof_headline 400 rocprofv3 --kernel-trace --stats -d $O/prof_headline -o run --output-format csv -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-epoch --no-eager-ref --timer none
 python3 tools/trace_step.py $O/prof_headline/run_kernel_trace.csv --marker k_slot_load --skip 8 --steps 10 > $O/step_headline.txt 2>&1
 cat $O/step_headline.txt
 echo done

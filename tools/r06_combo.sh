@@ -17,12 +17,12 @@ if [ -n "${PYTEST_K:-}" ]; then
   tail -3 $O/pytest.log
 fi
 if [ "${HEADLINE:-1}" = 1 ]; then
-  step bench_headline 400 python3 bench.py --no-cpu-baseline
+  step bench_headline 400 python3 bench.py --full --no-cpu-baseline
   tail -1 $O/bench_headline.log | cut -c1-400
-  step prof_headline 400 rocprofv3 --kernel-trace --stats -d $O/prof_headline -o run --output-format csv -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-epoch --timer none
+  step prof_headline 400 rocprofv3 --kernel-trace --stats -d $O/prof_headline -o run --output-format csv -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-epoch --timer none
   python3 tools/trace_step.py $O/prof_headline/run_kernel_trace.csv --marker k_slot_load --skip 8 --steps 10 > $O/step_headline.txt 2>&1
   head -12 $O/step_headline.txt
-  step prof_epoch 400 rocprofv3 --kernel-trace --stats -d $O/prof_epoch -o run --output-format csv -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-eager-ref --timer none
+  step prof_epoch 400 rocprofv3 --kernel-trace --stats -d $O/prof_epoch -o run --output-format csv -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-eager-ref --timer none
   python3 tools/epoch_trace.py $O/prof_epoch/run_kernel_trace.csv --batches 190 > $O/epoch_breakdown.txt 2>&1
   head -30 $O/epoch_breakdown.txt
 fi
@@ -36,7 +36,7 @@ fi
 for i in 1 2 3 4; do
   eval "A=\${BENCH_ARGS_$i:-}"
   if [ -n "$A" ]; then
-    step bench_x$i 400 python3 bench.py --no-cpu-baseline $A
+    step bench_x$i 400 python3 bench.py --full --no-cpu-baseline $A
     tail -1 $O/bench_x$i.log | cut -c1-500
   fi
 done

@@ -15,8 +15,8 @@ step() {
 }
 step pytest 900 python -u -m pytest tests -m gpu -q -x --timeout 300 --timeout-method thread
 step smoke 300 python3 -c "import __graft_entry__ as g; g.smoke()"
-step bench_default 600 python3 bench.py
-step prof_headline 400 rocprofv3 --kernel-trace --stats -d $O/prof_headline -o run --output-format csv -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-epoch --no-eager-ref --timer none
+step bench_default 600 python3 bench.py --full
+step prof_headline 400 rocprofv3 --kernel-trace --stats -d $O/prof_headline -o run --output-format csv -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-epoch --no-eager-ref --timer none
 python3 tools/trace_step.py $O/prof_headline/run_kernel_trace.csv --marker k_slot_load --skip 8 --steps 10 > $O/step_headline.txt 2>&1
 head -8 $O/step_headline.txt
 for c in ${BENCHES:-computers gcn arxiv p3_ref coteaching}; do
@@ -29,6 +29,6 @@ for c in ${BENCHES:-computers gcn arxiv p3_ref coteaching}; do
     gcn) A="--module gcn" ;;
     coteaching) A="--coteaching" ;;
   esac
-  step bench_$c 400 python3 bench.py --no-cpu-baseline --no-eager-ref $A
+  step bench_$c 400 python3 bench.py --full --no-cpu-baseline --no-eager-ref $A
 done
 echo done

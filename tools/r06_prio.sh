@@ -12,6 +12,6 @@ step() {
   if [ $rc -ne 0 ]; then exit $rc; fi
 }
 for p in 0 -1 0 -1; do
-  NGNN_SIDE_PRIORITY=$p step bench_p$p 400 python3 bench.py --no-cpu-baseline --no-eager-ref
+  NGNN_SIDE_PRIORITY=$p step bench_p$p 400 python3 bench.py --full --no-cpu-baseline --no-eager-ref
 done
 echo done

@@ -24,7 +24,7 @@ elif [ -n "${PYTEST_K:-}" ]; then
   tail -3 $O/pytest.log
 fi
 if [ "${DP:-0}" = 1 ]; then
-  NGNN_DIST_BACKEND=gloo step dp2 400 python3 bench.py --gpus 2 --steps 20 --warmup 5 --scale 0.1 --no-cpu-baseline --no-epoch
+  NGNN_DIST_BACKEND=gloo step dp2 400 python3 bench.py --full --gpus 2 --steps 20 --warmup 5 --scale 0.1 --no-cpu-baseline --no-epoch
   tail -1 $O/dp2.log | cut -c1-600
 fi
 for c in ${BENCHES:-}; do
@@ -39,10 +39,10 @@ for c in ${BENCHES:-}; do
     p3_ref) A="--fanout 15,10,5 --batch-size 512 --steps 20 --warmup 5" ;;
     gcn) A="--module gcn" ;;
   esac
-  step bench_$c 400 python3 bench.py --no-cpu-baseline $A
+  step bench_$c 400 python3 bench.py --full --no-cpu-baseline $A
   tail -1 $O/bench_$c.log | cut -c1-300
   if [ "${PROF:-0}" = 1 ]; then
-    step prof_$c 400 rocprofv3 --kernel-trace --stats -d $O/prof_$c -o run --output-format csv -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-epoch --timer none $A
+    step prof_$c 400 rocprofv3 --kernel-trace --stats -d $O/prof_$c -o run --output-format csv -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-epoch --timer none $A
     python3 tools/trace_step.py $O/prof_$c/run_kernel_trace.csv --marker k_slot_load --skip 8 --steps 10 > $O/step_$c.txt 2>&1
     head -24 $O/step_$c.txt
   fi

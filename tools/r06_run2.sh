@@ -30,13 +30,13 @@ fi
 for i in 1 2 3 4; do
   eval "A=\${BENCH_ARGS_$i:-}"
   if [ -n "$A" ]; then
-    step bench_x$i 400 python3 bench.py --no-cpu-baseline $A
+    step bench_x$i 400 python3 bench.py --full --no-cpu-baseline $A
     tail -1 $O/bench_x$i.log | cut -c1-300
   fi
 done
 if [ -n "${PMC_ARGS:-}" ]; then
   for c in FETCH_SIZE WRITE_SIZE; do
-    step pmc_$c 300 rocprofv3 --kernel-trace --pmc $c --kernel-include-regex "${PMC_RE:-k_sage_rt}" -d $O/pmc_$c -o run --output-format csv -- python3 bench.py --no-cpu-baseline --no-epoch --no-eager-ref --timer none $PMC_ARGS
+    step pmc_$c 300 rocprofv3 --kernel-trace --pmc $c --kernel-include-regex "${PMC_RE:-k_sage_rt}" -d $O/pmc_$c -o run --output-format csv -- python3 bench.py --full --no-cpu-baseline --no-epoch --no-eager-ref --timer none $PMC_ARGS
   done
 fi
 echo done

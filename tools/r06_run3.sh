@@ -20,9 +20,9 @@ step eager_cprof 200 python3 tools/eager_step.py --cprofile
 grep -v amdgpu $O/eager_cprof.log | head -50
 step eager_sec 200 python3 tools/eager_sections.py
 grep -v amdgpu $O/eager_sec.log
-step bench_headline 400 python3 bench.py --no-cpu-baseline
+step bench_headline 400 python3 bench.py --full --no-cpu-baseline
 tail -1 $O/bench_headline.log | cut -c1-300
-step prof_epoch 400 rocprofv3 --kernel-trace --stats -d $O/prof_epoch -o run --output-format csv -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-eager-ref --timer none
+step prof_epoch 400 rocprofv3 --kernel-trace --stats -d $O/prof_epoch -o run --output-format csv -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-eager-ref --timer none
 python3 tools/epoch_trace.py $O/prof_epoch/run_kernel_trace.csv --batches 190 --skip-last 193 > $O/epoch_breakdown_sf.txt 2>&1
 python3 tools/epoch_trace.py $O/prof_epoch/run_kernel_trace.csv --batches 190 --skip-last 386 > $O/epoch_breakdown_sync.txt 2>&1
 python3 tools/epoch_trace.py $O/prof_epoch/run_kernel_trace.csv --batches 190 > $O/epoch_breakdown_fg.txt 2>&1

@@ -26,10 +26,10 @@ for c in ${BENCHES:-computers}; do
     gcn) A="--module gcn" ;;
     coteaching) A="--coteaching" ;;
   esac
-  step bench_$c 400 python3 bench.py --no-cpu-baseline $A
+  step bench_$c 400 python3 bench.py --full --no-cpu-baseline $A
   tail -1 $O/bench_$c.log | cut -c1-250
   if [ "${PROF:-1}" = 1 ]; then
-    step prof_$c 400 rocprofv3 --kernel-trace --stats -d $O/prof_$c -o run --output-format csv -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-epoch --no-eager-ref --timer none $A
+    step prof_$c 400 rocprofv3 --kernel-trace --stats -d $O/prof_$c -o run --output-format csv -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-epoch --no-eager-ref --timer none $A
     python3 tools/trace_step.py $O/prof_$c/run_kernel_trace.csv --marker k_slot_load --skip 8 --steps 10 > $O/step_$c.txt 2>&1
     head -3 $O/step_$c.txt
   fi

@@ -13,8 +13,8 @@ step() {
 }
 step smoke 300 python3 -c "import __graft_entry__ as g; g.smoke()"
 tail -1 $O/smoke.log
-NGNN_DIST_BACKEND=gloo step dp2_headline 600 python3 bench.py --gpus 2 --steps 10 --warmup 3 --no-cpu-baseline --no-eager-ref
+NGNN_DIST_BACKEND=gloo step dp2_headline 600 python3 bench.py --full --gpus 2 --steps 10 --warmup 3 --no-cpu-baseline --no-eager-ref
 tail -1 $O/dp2_headline.log | cut -c1-400
-NGNN_DIST_BACKEND=gloo step dp2_coteaching 600 python3 bench.py --gpus 2 --steps 10 --warmup 3 --no-cpu-baseline --no-eager-ref --coteaching
+NGNN_DIST_BACKEND=gloo step dp2_coteaching 600 python3 bench.py --full --gpus 2 --steps 10 --warmup 3 --no-cpu-baseline --no-eager-ref --coteaching
 tail -1 $O/dp2_coteaching.log | cut -c1-300
 echo done

@@ -19,7 +19,7 @@ for pass in 1 2; do
 done
 for v in tree f2prio b2prio tree; do
   if [ $v = tree ]; then L=""; else L=$PWD/abv/libngnn_$v.so; fi
-  NGNN_LIB=$L timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-eager-ref --no-epoch > $O/bench_$v.log 2>&1 || exit 3
+  NGNN_LIB=$L timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-eager-ref --no-epoch > $O/bench_$v.log 2>&1 || exit 3
   echo "bench $v $(tail -1 $O/bench_$v.log | python3 -c 'import json,sys; print(json.loads(sys.stdin.read())["ms_per_step"])')" | tee -a $O/summary.txt
 done
 echo done
