@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define NGNN_ABI_VERSION 21
+#define NGNN_ABI_VERSION 22
 
 /* error codes (negative); positive values are hipError_t */
 #define NGNN_OK 0
@@ -217,6 +217,61 @@ int ngnn_sample_block_finish(const int32_t *fanouts, int n_hops, int64_t n_seeds
                              const float *x_all, int64_t ldx, int64_t F, float *x, int64_t ldo,
                              int64_t n_active, int32_t *csr_rowptr, int32_t *csr_col,
                              const int32_t *counts_dev, void *stream);
+
+/* ------------------------------------------- block-free layer-wise inference
+ * ABI 22.  SAGE.inference / SimpleGCN.inference (sage.py:42-58,
+ * convolution.py:37-53; called per epoch by test_ogb, pipeline.py:291) run
+ * each layer over every node: per loader batch the conv on a whole multi-hop
+ * block, of which only the seed rows are kept.  A seed row receives in-edges
+ * from hop 0 alone (a later hop's frontier is the newly reached nodes), and
+ * hop 0's draws depend only on (block seed, position in the batch, degree) --
+ * so the kept rows need no block.  Both entries address a run of LOADER
+ * POSITIONS p = r0 .. r0 + n_rows - 1 of a pass whose batches hold batch_size
+ * seeds (r0 a multiple of batch_size: NGNN_E_ARG otherwise):
+ *   batch b = p / batch_size, position i = p % batch_size,
+ *   block seed S_b = seed0 + b * seed_stride (uint64 wrap-around), hop seed
+ *   S_b * 1000003 + 0 (ngnn_sample_block's hop 0),
+ *   node v = seeds ? seeds[p] : p   (seeds: int64, indexed by p; nullable),
+ *   draws = ngnn_sample_hop's for (deg(v), fanout, hop seed, i): min(deg,
+ *   fanout) distinct in-neighbours of the graph CSR (g_rowptr int64[N + 1],
+ *   g_col int32) in Floyd order; deg <= fanout keeps every neighbour in CSR
+ *   order, multi-edges included -- bitwise the in-edges NeighborLoader's block
+ *   gives seed row i of batch b.
+ * fanout > 64: NGNN_E_SHAPE; a negative size: NGNN_E_ARG; n_rows * fanout >=
+ * 2^31: NGNN_E_RANGE -- nothing is launched.
+ *
+ * ngnn_infer_draw: the draws as a target-grouped CSR, rowptr int32[n_rows + 1]
+ * and col int32[rowptr[n_rows]] (the caller sizes col for n_rows * fanout):
+ * col holds GLOBAL node ids in draw order inside a row -- the col_x (with
+ * xrow = the positions' nodes) of ngnn_sage_fwd_raw's fused gather, which then
+ * reads the previous layer's table in place: no x[n_id] copy, no relabelling.
+ * Three launches (counts + tile scan, tile offsets, one lane group per row
+ * drawing).  ws: ngnn_infer_draw_workspace_bytes(n_rows), 4-B aligned.
+ *
+ * ngnn_infer_narrow: a narrowing layer's rows with the draws made in the
+ * kernel (no CSR materialised), the neighbour term reduced F_out wide:
+ *   out[r, c] = act(root[r, c] + red_j z[nbr_j(r), c] + bias[c]),  c < Fo,
+ *   r < n_rows (row r = position r0 + r), red = MEAN (0 for an empty row) or
+ *   SUM (NGNN_REDUCE_*; MAX is not linear: NGNN_E_ARG), act = ReLU if relu.
+ * z [N, ldz] = x W_l^T for EVERY node (fp32, 16-B aligned, ldz a multiple of
+ * 4 and >= ceil4(Fo)); root [n_rows, ld_root] (same layout rules; row r of the
+ * chunk) = x W_r^T (+ b) of the positions' nodes, NULL for GCNConv (no root
+ * term); bias nullable (NULL when root already carries it).  out [n_rows,
+ * ldo]: the caller's row pointer and stride (the next table at the chunk's
+ * row offset).  Equal to the K-wide aggregate followed by W_l up to fp32
+ * rounding (NGNN_FWD_NARROW's identity).  Plain vector stores only.
+ * Replaces, for whole-graph evaluation, NeighborLoader's block + x[n_id] +
+ * PyG SAGEConv / GCNConv forward [ext] + the [:batch_size] slice. */
+size_t ngnn_infer_draw_workspace_bytes(int64_t n_rows);
+int ngnn_infer_draw(const int64_t *g_rowptr, const int32_t *g_col, const int64_t *seeds, int64_t r0,
+                    int64_t n_rows, int64_t batch_size, int fanout, uint64_t seed0,
+                    uint64_t seed_stride, int32_t *rowptr, int32_t *col, void *ws, size_t ws_bytes,
+                    void *stream);
+int ngnn_infer_narrow(const int64_t *g_rowptr, const int32_t *g_col, const int64_t *seeds, int64_t r0,
+                      int64_t n_rows, int64_t batch_size, int fanout, uint64_t seed0,
+                      uint64_t seed_stride, const float *z, int64_t ldz, const float *root,
+                      int64_t ld_root, const float *bias, int64_t Fo, int reduce, int relu, float *out,
+                      int64_t ldo, void *stream);
 
 /* ------------------------------------------------------ co-teaching loss
  * CTLoss.forward (src/utils/losses.py:19-49) without its two host argsorts:

@@ -14,41 +14,14 @@
 #include <algorithm>
 
 #include "ngnn_internal.h"
+#include "ngnn_sample_dev.h"
 
 namespace ngnn {
 namespace {
 
-constexpr int kMaxFanout = 64;
 constexpr int kMaxHops = 8;
 
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-// min(d, k) distinct CSR positions of a degree-d row, Floyd order; d <= k:
-// all positions in CSR order.  Keyed by (seed, frontier position i).
-__device__ __forceinline__ int floyd_sample(int64_t d, int fanout, uint64_t seed, int64_t i,
-                                            int64_t (&sel)[kMaxFanout]) {
-    const int k = d < fanout ? static_cast<int>(d) : fanout;
-    if (d <= fanout) {
-        for (int j = 0; j < k; ++j) sel[j] = j;
-        return k;
-    }
-    const uint64_t base = mix64(seed ^ mix64(static_cast<uint64_t>(i) + 0x632BE59BD9B4E019ull));
-    int m = 0;
-    for (int64_t j = d - k; j < d; ++j) {
-        const uint64_t r = mix64(base + static_cast<uint64_t>(j));
-        const int64_t t = static_cast<int64_t>(
-            (static_cast<unsigned __int128>(r) * static_cast<uint64_t>(j + 1)) >> 64);
-        bool dup = false;
-        for (int q = 0; q < m; ++q) dup |= sel[q] == t;
-        sel[m++] = dup ? j : t;
-    }
-    return k;
-}
+// (mix64, floyd_sample, floyd_lane, sb_kf: ngnn_sample_dev.h, shared with ngnn_infer.hip)
 
 __global__ __launch_bounds__(256) void k_sample_hop(const int64_t *__restrict__ rowptr,
                                                     const int32_t *__restrict__ gcol,
@@ -116,36 +89,8 @@ __global__ __launch_bounds__(kSbBlock) void k_sb_init(const int64_t *__restrict_
     }
 }
 
-// Lane-per-draw layout (round 6): frontier position i owns a group of KF
-// lanes (KF = fanout rounded up to 8/16/32/64, a power of two dividing the
-// wave), lane j its draw j.  The per-thread layout before it ran one thread
-// per position -- 60 workgroups for a products hop-2 frontier, each thread a
-// serial chain of draws, loads and atomics -- latency-bound at ~30 us a
-// launch.  Floyd's draws are independent but for the duplicate test: draw q's
-// final choice is known once draws < q are, so the group resolves them in
-// fanout - 1 shuffle rounds (lane q's choice broadcast, later lanes compare).
-// Same selections as floyd_sample.
-template <int KF>
-__device__ __forceinline__ int floyd_lane(int64_t d, int fanout, uint64_t seed, int i, int j, int &k) {
-    k = d < fanout ? static_cast<int>(d) : fanout;
-    if (d <= fanout) return j;
-    const uint64_t base = mix64(seed ^ mix64(static_cast<uint64_t>(i) + 0x632BE59BD9B4E019ull));
-    const int64_t J = d - k + j;  // (lanes j >= k compute a value nobody reads)
-    const uint64_t r = mix64(base + static_cast<uint64_t>(J));
-    const int32_t t = static_cast<int32_t>((static_cast<unsigned __int128>(r) * static_cast<uint64_t>(J + 1)) >> 64);
-    const int32_t jw = static_cast<int32_t>(J);
-    bool dup = false;
-    for (int q = 0; q < k - 1; ++q) {  // (k is uniform over the group; every source lane is active)
-        const int32_t fq = __shfl(dup ? jw : t, q, KF);
-        dup |= j > q && fq == t;
-    }
-    return dup ? jw : t;
-}
-
 constexpr int kSbTile = 1024;  // k_sb_count / k_sb_write's tile: kSbTile / KF frontier positions
 constexpr int kSbChunks = kSbTile / 64;  // its wave chunks
-
-__host__ __device__ constexpr int sb_kf(int f) { return f <= 8 ? 8 : f <= 16 ? 16 : f <= 32 ? 32 : 64; }
 
 // draw j of frontier node i -> cand[i*f + j]; claims first appearances.
 // Also (one launch fewer per hop): the previous hop's edges relabelled to
@@ -523,7 +468,7 @@ extern "C" int ngnn_sample_block(const int64_t *g_rowptr, const int32_t *g_col, 
         const int sgrid = static_cast<int>(std::max<int64_t>(1, ceil_div(nf * kf, kSbBlock)));
         int32_t *cand = w.cand + p.cand_off[h], *cnt = w.cnt + p.cnt_off[h];
         // the per-hop seed of ngnn_sample_hop's callers (loader.sample_block)
-        const uint64_t hseed = seed * 1000003ull + static_cast<uint64_t>(h);
+        const uint64_t hseed = hop_seed(seed, h);
         // three launches per hop (round 6; five before): draws + claims (+ the
         // previous hop's relabel), the first-appearance counts, the writes
         auto hop = [&](auto kf_c) {

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # NGNN_LIB: an alternative build of the same ABI (A/B kernel experiments);
 # read once, at import
 LIB_PATH = os.environ.get("NGNN_LIB") or os.path.join(_HERE, "lib", "libngnn.so")
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 OK = 0
 SLOT_UNSORTED = 1  # ngnn_slot_load's err bits (include/ngnn.h NGNN_SLOT_*)
@@ -49,6 +49,11 @@ SIGNATURES = {
                                  _p]),
     "ngnn_sample_block_finish": (_int, [_p, _int, _i64, _i64, _i64, _p, _i64, _p, _sz, _p, _p, _p,
                                         _p, _p, _i64, _i64, _p, _i64, _i64, _p, _p, _p, _p]),
+    "ngnn_infer_draw_workspace_bytes": (_sz, [_i64]),
+    "ngnn_infer_draw": (_int, [_p, _p, _p, _i64, _i64, _i64, _int, ctypes.c_uint64, ctypes.c_uint64, _p, _p,
+                               _p, _sz, _p]),
+    "ngnn_infer_narrow": (_int, [_p, _p, _p, _i64, _i64, _i64, _int, ctypes.c_uint64, ctypes.c_uint64, _p, _i64,
+                                 _p, _i64, _p, _i64, _int, _int, _p, _i64, _p]),
     "ngnn_pack_weight_bytes": (_sz, [_i64, _i64]),
     "ngnn_pack_weight": (_int, [_p, _i64, _i64, _i64, _p, _p]),
     "ngnn_pack_weight_ex": (_int, [_p, _p, _i64, _i64, _i64, _i64, _int, _p, _p]),

@@ -514,6 +514,13 @@ class NeighborLoader:
         return shard_seeds(self.input_nodes, self.rank, self.world_size, self.epoch, self.seed,
                            shuffle=self.shuffle)
 
+    def batch_seed(self, ep: int, b: int) -> int:
+        """The block seed of batch ``b`` of this loader's pass number ``ep``
+        (its ``epoch`` when the pass began): what ``__iter__`` hands the
+        sampler, and what a block-free consumer of the same draws
+        (ngnn.models' fused inference plan) derives them from."""
+        return (self.seed * 7919 + ep) * 100_003 + b * self.world_size + self.rank
+
     def __len__(self):
         from .distributed import shard_len
         n = shard_len(self.input_nodes.numel(), self.world_size)
@@ -551,7 +558,7 @@ class NeighborLoader:
             s = seeds[b * self.batch_size:(b + 1) * self.batch_size]
             with torch.cuda.stream(side):
                 return _sample_start(self.graph, s, self.num_neighbors,
-                                     seed=(self.seed * 7919 + ep) * 100_003 + b * self.world_size + self.rank,
+                                     seed=self.batch_seed(ep, b),
                                      gather_features=self.gather_features, state=state, slot=b & 1)
 
         pending = None
@@ -604,7 +611,7 @@ class NeighborLoader:
                     if done[b & 1] is not None:
                         side.wait_event(done[b & 1])
                     blk = _sample_sync_free(self.graph, s, self.num_neighbors,
-                                            (self.seed * 7919 + ep) * 100_003 + b * self.world_size + self.rank,
+                                            self.batch_seed(ep, b),
                                             self.gather_features, states[b & 1])
                     ready = torch.cuda.Event()
                     ready.record(side)

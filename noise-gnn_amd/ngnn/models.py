@@ -17,8 +17,9 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import fused
+from . import fused, infer
 from .block import get_block
+from .infer import last_inference_plan  # noqa: F401  (per layer: "rowtile" / "narrow" / "loop")
 from .loader import IndexedRows
 from .nn import GCNConv, SAGEConv
 
@@ -101,8 +102,13 @@ class SAGE(nn.Module):
         the result is returned where ``x_all`` was given.  Between layers the
         activations stay on the device (the reference round-trips every batch
         through the host, sage.py:50,56).
+
+        With an in-order ``ngnn.loader.NeighborLoader`` over every node the
+        same rows are computed without building a block (ngnn.infer: the seed
+        rows' hop-0 draws straight from the graph CSR; ``last_inference_plan``
+        names each layer's path).
         """
-        return _layerwise_inference(self.convs, self.num_layers, x_all, subgraph_loader, device)
+        return _inference(self.convs, self.num_layers, x_all, subgraph_loader, device)
 
 
 class SimpleGCN(nn.Module):
@@ -138,8 +144,21 @@ class SimpleGCN(nn.Module):
 
     @torch.no_grad()
     def inference(self, x_all, subgraph_loader, device):
-        """convolution.py:37-53 semantics (same loop as SAGE.inference)."""
-        return _layerwise_inference(self.convs, self.num_layers, x_all, subgraph_loader, device)
+        """convolution.py:37-53 semantics (same loop, and the same block-free
+        plan, as SAGE.inference)."""
+        return _inference(self.convs, self.num_layers, x_all, subgraph_loader, device)
+
+
+def _inference(convs, num_layers, x_all, subgraph_loader, device):
+    """The block-free plan (ngnn.infer) when the loader is an in-order ngnn
+    NeighborLoader over every node and the model is fp32; the reference loop
+    for everything else (generic iterables of batches, shuffled or permuted
+    seeds, sharded or sync-free loaders)."""
+    if infer.eligible(convs, x_all, subgraph_loader, device):
+        return infer.fused_inference(convs, num_layers, x_all, subgraph_loader, device)
+    out = _layerwise_inference(convs, num_layers, x_all, subgraph_loader, device)
+    last_inference_plan[:] = ["loop"] * num_layers
+    return out
 
 
 def _layerwise_inference(convs, num_layers, x_all, subgraph_loader, device):

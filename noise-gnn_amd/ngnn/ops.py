@@ -86,3 +86,19 @@ def segment_aggregate(x: torch.Tensor, block: Block, reduce: str = "mean") -> to
     if reduce not in _lib.REDUCE:
         raise ValueError(f"unsupported aggregation {reduce!r} (expected mean, sum/add or max)")
     return _SegmentAggregate.apply(x, block, reduce)
+
+
+def sample_seed_rows(graph, fanout: int, batch_size: int, seed0: int, seed_stride: int, r0: int,
+                     n_rows: int, seeds=None):
+    """The hop-0 draws of loader positions ``r0 .. r0 + n_rows - 1`` of a pass
+    with ``batch_size`` seeds per batch, without building a block
+    (``ngnn_infer_draw``): position ``p`` is seed ``i = p % batch_size`` of
+    batch ``b = p // batch_size``, whose block seed is ``seed0 + b *
+    seed_stride`` (``NeighborLoader.batch_seed``); its node is ``seeds[p]``
+    (``p`` itself without ``seeds``).  Returns the target-grouped CSR
+    ``(rowptr int32[n_rows + 1], col int32[nnz])`` of GLOBAL neighbour ids in
+    draw order -- bitwise the in-edges the loader's block gives that seed row.
+    ``r0`` must be a multiple of ``batch_size``.  One host read (nnz)."""
+    from .infer import seed_rows
+    rowptr, col = seed_rows(graph, int(fanout), int(batch_size), seed0, seed_stride, int(r0), int(n_rows), seeds)
+    return rowptr, col[:int(rowptr[-1])]
