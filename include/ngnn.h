@@ -793,6 +793,48 @@ int ngnn_slot_load(const float *x, int64_t ldx, int64_t N, int64_t F, const int6
                    int64_t pack_k, float *pack_dst, int32_t *err, const int32_t *counts_dev,
                    uint64_t *gate, void *stream);
 
+/* --------------------------------------------- SAGEPL's per-node input noise
+ * Added within ABI 22 (new entries only: nothing existing changed, so the
+ * version did not move).  SAGEPL.adding_noise (src/models/layers/sagePL.py:
+ * 41-49) in one launch, and its backward in one launch.  fp32 only, any
+ * F >= 1.  For row i < n_rows, id = n_id ? n_id[i] : i (n_id int64, nullable;
+ * NULL needs n_rows == n_nodes), v = noise[id, :F] of the table noise
+ * [n_nodes, ldn], d = max(||v||_2, 1e-12) -- F.normalize(dim=1) as torch
+ * defines it:
+ *   fwd:  out[i, f] = x[i, f] + s * (v[f] / d) * rate
+ *         s = 1, or sign(x[i, f]) with sign(0) = 0 under NGNN_NOISE_SIGN (the
+ *         reference's n_id=None branch, sagePL.py:44)
+ *   bwd:  gs = g[i, :] * rate * s,  u = v / d,
+ *         dv = (gs - u <u, gs>) / d   if ||v|| >= 1e-12,  else  gs / 1e-12
+ *         (clamp_min's backward: a zero row gets a large finite gradient, as
+ *         in torch); the norm is recomputed from the table row, x is read
+ *         only under NGNN_NOISE_SIGN (nullable otherwise)
+ *         scatter = 1: dnoise[id, :] += dv by float atomics into the caller's
+ *           zeroed [n_nodes, ldd] buffer (duplicate ids accumulate, as
+ *           index_add_; the sum's last bits depend on arrival order)
+ *         scatter = 0: dnoise[i, :] = dv, plain stores into [n_rows, ldd]
+ *           (bitwise reproducible; the caller sums duplicates)
+ * An id outside [0, n_nodes) neither reads nor writes the table: forward
+ * copies x to out for that row, backward contributes nothing (scatter = 0
+ * stores a zero row); each adds 1 to *bad (device int32, nullable).
+ * 16-B accesses when the bases and leading dimensions allow, dword accesses
+ * otherwise; a lane group per row, row sums by cross-lane shuffles; no
+ * allocation, no host synchronisation (safe under stream capture).
+ * n_rows == 0 or F == 0: success, no pointer is read.  Before any launch:
+ * a negative size, an unknown flag, scatter not 0 / 1, n_id NULL with n_rows
+ * != n_nodes, a NULL data pointer: NGNN_E_ARG; a leading dimension < F:
+ * NGNN_E_SHAPE; n_rows or F >= 2^31: NGNN_E_RANGE.
+ * Replaces x.clone(), noise[n_id], F.normalize, the scale and the add (and
+ * their autograd backwards with index_add_) [ext: torch]. */
+#define NGNN_NOISE_SIGN 1
+int ngnn_node_noise_fwd(const float *x, int64_t ldx, const float *noise, int64_t ldn, int64_t n_nodes,
+                        const int64_t *n_id, int64_t n_rows, int64_t F, float rate, int flags,
+                        float *out, int64_t ldo, int32_t *bad, void *stream);
+int ngnn_node_noise_bwd(const float *g, int64_t ldg, const float *x, int64_t ldx, const float *noise,
+                        int64_t ldn, int64_t n_nodes, const int64_t *n_id, int scatter, int64_t n_rows,
+                        int64_t F, float rate, int flags, float *dnoise, int64_t ldd, int32_t *bad,
+                        void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,8 +1,9 @@
-"""Drop-in model wrappers: ``SAGE``, ``SimpleGCN`` and the ``NGNN`` factory.
+"""Drop-in model wrappers: ``SAGE``, ``SAGEPL``, ``SimpleGCN`` and the ``NGNN`` factory.
 
 Mirror the reference classes one to one:
 
 * ``SAGE``      src/models/layers/sage.py:6-79
+* ``SAGEPL``    src/models/layers/sagePL.py:6-94
 * ``SimpleGCN`` src/models/layers/convolution.py:7-53
 * ``NGNN``      src/models/model.py:10-69 (module string -> network, Adam optimiser)
 
@@ -22,6 +23,7 @@ from .block import get_block
 from .infer import last_inference_plan  # noqa: F401  (per layer: "rowtile" / "narrow" / "loop")
 from .loader import IndexedRows
 from .nn import GCNConv, SAGEConv
+from .ops import add_node_noise
 
 
 def _refuse_sync_free(edge_index):
@@ -149,6 +151,90 @@ class SimpleGCN(nn.Module):
         return _inference(self.convs, self.num_layers, x_all, subgraph_loader, device)
 
 
+class SAGEPL(nn.Module):
+    """The reference's ``SAGEPL`` (src/models/layers/sagePL.py:6-94, what
+    ``module: 'sagePL'`` selects): a GraphSAGE stack with a learnable noise
+    table ``noise [nbr_nodes, in_size]``.  Each call runs a pure pass on ``x``
+    and a noisy pass on ``x + noise_rate * normalize(noise[n_id])`` over one
+    shared block and returns ``(h_pure, logp_pure, z_pure, h_noisy,
+    logp_noisy, z_noisy)``: ``h`` the last hidden activation (after ReLU and
+    ``bn2``, before dropout), ``z`` the logits, ``logp = log_softmax(z, 1)``.
+
+    The noise add and its backward are one launch each
+    (``ngnn.ops.add_node_noise``); every layer runs the per-conv path, whose
+    layer 0 hands back the input gradient that trains the table.  State-dict
+    keys are the reference's (``noise``, ``convs.{i}.lin_l.weight`` ...).
+
+    ``num_layers >= 2``: with one layer the reference's ``h`` is never
+    assigned (sagePL.py:60 runs for hidden layers only) and its forward
+    raises; here the constructor does.  The noise path is fp32 only.
+    """
+
+    def __init__(self, in_size, hidden_size, out_size, num_layers, nbr_nodes, dropout=0.5,
+                 use_bn=False, aggr: str = "mean"):
+        super().__init__()
+        if num_layers < 2:
+            raise ValueError("SAGEPL needs num_layers >= 2: the hidden state it returns is the last "
+                             "hidden layer's (undefined in the reference for one layer)")
+        self.num_layers = num_layers
+        self.dropout = dropout
+        self.convs = nn.ModuleList()
+        self.convs.append(SAGEConv(in_size, hidden_size, aggr=aggr))
+        for _ in range(num_layers - 2):
+            self.convs.append(SAGEConv(hidden_size, hidden_size, aggr=aggr))
+        self.convs.append(SAGEConv(hidden_size, out_size, aggr=aggr))
+        # adaptive noise to be added (sagePL.py:22)
+        self.noise = nn.Parameter(torch.randn(nbr_nodes, in_size))
+        self.use_bn = use_bn
+        if self.use_bn:
+            self.bn1 = nn.BatchNorm1d(in_size)
+            self.bn2 = nn.BatchNorm1d(hidden_size)
+
+    def reset_parameters(self):
+        for conv in self.convs:  # (the convs only, as the reference: sagePL.py:29-31)
+            conv.reset_parameters()
+
+    def forward(self, x, edge_index, noise_rate=0.1, n_id=None):
+        _refuse_sync_free(edge_index)
+        if isinstance(x, IndexedRows):  # eager: gather the rows
+            x = x.materialize()
+        block = get_block(edge_index, x.size(0))  # built once, shared by both passes
+        pure = self._stack(x, block)
+        noisy_x = self.adding_noise(x, noise_rate=noise_rate, n_id=n_id)
+        return pure + self._stack(noisy_x, block)
+
+    def adding_noise(self, x, noise_rate, n_id=None):
+        # n_id=None: the sign branch over the whole table (sagePL.py:43-44)
+        return add_node_noise(x, self.noise, n_id=n_id, rate=noise_rate, sign=n_id is None)
+
+    def _stack(self, x, block):
+        if self.use_bn:
+            x = self.bn1(x)
+        for i, conv in enumerate(self.convs):
+            x = conv(x, block)
+            if i != self.num_layers - 1:
+                x = x.relu()
+                if self.use_bn:
+                    x = self.bn2(x)
+                h = x
+                x = F.dropout(x, p=self.dropout, training=self.training)
+        return h, torch.log_softmax(x, dim=1), x
+
+    def forward_pure(self, x, edge_index):
+        _refuse_sync_free(edge_index)
+        return self._stack(x, get_block(edge_index, x.size(0)))
+
+    def forward_noisy(self, x, edge_index):
+        _refuse_sync_free(edge_index)
+        return self._stack(x, get_block(edge_index, x.size(0)))
+
+    @torch.no_grad()
+    def inference(self, x_all, subgraph_loader, device):
+        """sagePL.py:78-94 semantics: the convs alone, the noise unused (same
+        loop, and the same block-free plan, as SAGE.inference)."""
+        return _inference(self.convs, self.num_layers, x_all, subgraph_loader, device)
+
+
 def _inference(convs, num_layers, x_all, subgraph_loader, device):
     """The block-free plan (ngnn.infer) when the loader is an in-order ngnn
     NeighborLoader over every node and the model is fp32; the reference loop
@@ -207,9 +293,13 @@ class NGNN(object):
             self.network = SAGE(in_size=self.in_size, hidden_size=self.hidden_size,
                                 out_size=self.out_size, num_layers=self.num_layers,
                                 dropout=self.dropout, use_bn=self.use_bn, aggr=self.aggr)
+        elif self.module == 'sagePL':  # model.py:57-63 (use_bn is not passed on there)
+            self.network = SAGEPL(in_size=self.in_size, hidden_size=self.hidden_size,
+                                  out_size=self.out_size, num_layers=self.num_layers,
+                                  dropout=self.dropout, nbr_nodes=self.nbr_nodes, aggr=self.aggr)
         else:
             raise ValueError(f"module {self.module!r} is outside this path "
-                             "(supported: 'sage', 'gcn'; see DESIGN.md scope)")
+                             "(supported: 'sage', 'sagePL', 'gcn'; see DESIGN.md scope)")
 
     def init_optimizer(self):
         if self.optimizer == 'adam':

@@ -102,3 +102,135 @@ def sample_seed_rows(graph, fanout: int, batch_size: int, seed0: int, seed_strid
     from .infer import seed_rows
     rowptr, col = seed_rows(graph, int(fanout), int(batch_size), seed0, seed_stride, int(r0), int(n_rows), seeds)
     return rowptr, col[:int(rowptr[-1])]
+
+
+# ---- SAGEPL's per-node input noise (ngnn_node_noise_fwd / _bwd) ----
+
+_bad_id_counters: dict = {}  # device index -> int32[1] on that device
+
+
+def _bad_id_counter(device: torch.device) -> torch.Tensor:
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    c = _bad_id_counters.get(idx)
+    if c is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("add_node_noise: call it once eagerly on this device before capturing "
+                               "(its bad-id counter is allocated at the first call)")
+        c = _bad_id_counters[idx] = torch.zeros(1, dtype=torch.int32, device=torch.device("cuda", idx))
+    return c
+
+
+def node_noise_bad_ids(device=None, reset: bool = False) -> int:
+    """How many rows ``add_node_noise``'s forward met on ``device`` with an id
+    outside the table (those rows pass ``x`` through and train nothing).
+    Debugging only: reading the device counter synchronises."""
+    dev = torch.device("cuda" if device is None else device)
+    c = _bad_id_counter(dev)
+    n = int(c.item())
+    if reset:
+        c.zero_()
+    return n
+
+
+def _row_major(t: torch.Tensor) -> torch.Tensor:
+    """t addressable as rows of stride(0) elements (a row-sliced or
+    column-sliced view passes as it is, through its leading dimension)."""
+    if t.stride(1) != 1 or (t.size(0) > 1 and t.stride(0) < t.size(1)):
+        return t.contiguous()
+    return t
+
+
+def _ld(t: torch.Tensor) -> int:
+    return max(t.stride(0), t.size(1)) if t.size(0) > 1 else t.size(1)
+
+
+class _AddNodeNoise(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, noise, n_id, rate: float, sign: bool):
+        xs, tab = _row_major(x), _row_major(noise)
+        n_rows, F = xs.shape
+        out = torch.empty(n_rows, F, dtype=xs.dtype, device=xs.device)
+        flags = _lib.NOISE_SIGN if sign else 0
+        bad = _bad_id_counter(xs.device)
+        # algorithmic bytes: x rows + table rows + out rows (+ the ids)
+        nbytes = 3 * n_rows * F * 4 + (0 if n_id is None else n_rows * 8)
+        with _timing.span("node_noise_fwd", nbytes):
+            rc = _lib.load().ngnn_node_noise_fwd(
+                _lib.ptr(xs), _ld(xs), _lib.ptr(tab), _ld(tab), tab.size(0), _lib.ptr(n_id), n_rows, F,
+                rate, flags, _lib.ptr(out), F, _lib.ptr(bad), _lib.stream_handle(xs.device))
+        _lib.check(rc, "ngnn_node_noise_fwd")
+        ctx.rate, ctx.flags = rate, flags
+        ctx.save_for_backward(xs if sign else None, tab, n_id)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        xs, tab, n_id = ctx.saved_tensors
+        dx = g if ctx.needs_input_grad[0] else None  # d out / d x = 1: the same tensor, no copy
+        if not ctx.needs_input_grad[1]:
+            return dx, None, None, None, None
+        gs = _row_major(g)
+        n_rows, F = gs.shape
+        n_nodes = tab.size(0)
+        # no id list: row i is table row i -- stored, nothing to zero or to add up
+        scatter = n_id is not None and not torch.are_deterministic_algorithms_enabled()
+        if scatter:
+            dst = dnoise = torch.zeros(n_nodes, F, dtype=gs.dtype, device=gs.device)
+        else:
+            dst = torch.empty(n_rows, F, dtype=gs.dtype, device=gs.device)
+        # algorithmic bytes: grad rows + table rows read, one row of adds / stores each
+        nbytes = 3 * n_rows * F * 4 + (0 if n_id is None else n_rows * 8)
+        with _timing.span("node_noise_bwd", nbytes):
+            rc = _lib.load().ngnn_node_noise_bwd(
+                _lib.ptr(gs), _ld(gs), _lib.ptr(xs), _ld(xs) if xs is not None else F, _lib.ptr(tab),
+                _ld(tab), n_nodes, _lib.ptr(n_id), int(scatter), n_rows, F, ctx.rate, ctx.flags,
+                _lib.ptr(dst), F, None, _lib.stream_handle(gs.device))
+        _lib.check(rc, "ngnn_node_noise_bwd")
+        if n_id is None:
+            dnoise = dst
+        elif not scatter:
+            # deterministic: the per-row gradients summed by torch's deterministic
+            # index_add_ (an id outside the table stored a zero row: any row takes it)
+            dnoise = torch.zeros(n_nodes, F, dtype=gs.dtype, device=gs.device)
+            dnoise.index_add_(0, n_id.clamp(0, max(n_nodes - 1, 0)), dst)
+        return dx, dnoise, None, None, None
+
+
+def add_node_noise(x: torch.Tensor, noise: torch.Tensor, n_id: torch.Tensor | None = None,
+                   rate: float = 0.1, sign: bool = False) -> torch.Tensor:
+    """``x + [sign(x) *] F.normalize(noise[n_id]) * rate`` as a new tensor --
+    the reference's ``SAGEPL.adding_noise`` (sagePL.py:41-49: ``x.clone()``,
+    the table gather, the row normalisation, the scale and the add) in one
+    launch; ``n_id=None`` takes the table's rows in order (``x`` must then
+    have one row per table row; the reference's branch there sets ``sign``).
+
+    Backward: ``dx`` is the incoming gradient itself; ``dnoise`` is dense
+    ``[nbr_nodes, F]`` (the reference's optimizer sees a dense gradient: Adam
+    moves every row's moments) -- a zero fill and one launch of float atomics,
+    duplicates accumulating as ``index_add_``.  Under
+    ``torch.use_deterministic_algorithms(True)`` the kernel stores one
+    gradient row per input row and torch's deterministic ``index_add_`` sums
+    them.  fp32, GPU only; an id outside the table passes its row of ``x``
+    through, trains nothing and is counted (``node_noise_bad_ids``)."""
+    for name, t in (("x", x), ("noise", noise)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"add_node_noise: {name} must be a CUDA tensor (no CPU fallback)")
+        if t.dtype != torch.float32:
+            raise ValueError(f"add_node_noise: {name} must be float32, got {t.dtype}")
+        if t.dim() != 2:
+            raise ValueError(f"add_node_noise: {name} must be 2-D, got shape {tuple(t.shape)}")
+    if x.device != noise.device:
+        raise ValueError(f"add_node_noise: x on {x.device}, noise on {noise.device}")
+    if x.size(1) != noise.size(1):
+        raise ValueError(f"add_node_noise: x is {x.size(1)} wide, the table {noise.size(1)}")
+    if n_id is None:
+        if x.size(0) != noise.size(0):
+            raise ValueError(f"add_node_noise: without n_id, x needs the table's {noise.size(0)} rows, "
+                             f"got {x.size(0)}")
+    else:
+        if not isinstance(n_id, torch.Tensor) or not n_id.is_cuda or n_id.dtype != torch.int64 \
+                or n_id.dim() != 1 or n_id.numel() != x.size(0) or n_id.device != x.device:
+            raise ValueError("add_node_noise: n_id must be an int64 CUDA tensor with one id per row of x")
+        n_id = n_id.contiguous()
+    return _AddNodeNoise.apply(x, noise, n_id, float(rate), bool(sign))
