@@ -728,7 +728,19 @@ int ngnn_cast_tensors_ex(int n, const void *const *src, void *const *dst, const 
 int ngnn_widen_bf16_rows(const void *src, int64_t lds, int64_t F, int64_t n_rows,
                          const int32_t *n_rows_dev, float *dst, int64_t ldd, void *stream);
 /* gate / gate_gen (ABI 20, nullable): as ngnn_adam_fold's -- the step of a
- * block that broke the graph slot's contract updates nothing. */
+ * block that broke the graph slot's contract updates nothing.
+ *
+ * State after a reload.  The call takes addresses only: *step is ONE count
+ * for all n_tensors (a parameter group), and exp_avgs[k] / exp_avg_sqs[k]
+ * are numels[k] fp32 values whatever dtypes[k] is.  A host that restores
+ * optimizer state must hand back that layout (torch's load_state_dict alone
+ * casts a bf16 model's moments to bf16 and copies the count per parameter);
+ * ngnn.optim.Adam.load_state_dict does, and Adam.step() checks it before a
+ * launch.  Counts that differ within a group, and a first gradient that
+ * arrives after the group's state was made, are errors there.  Against a
+ * float64 restatement the error is at most 2.1 x max(torch's own, half an
+ * fp32 ulp of the tensor's largest value) per tensor for p and both moments
+ * (profiles/adam_errors.jsonl). */
 int ngnn_adam_step(int n_tensors, float *const *params, const float *const *grads,
                    float *const *exp_avgs, float *const *exp_avg_sqs, const int64_t *numels,
                    const int32_t *dtypes, float *step, uint32_t *ticket, float lr, float beta1, float beta2, float eps,

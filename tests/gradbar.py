@@ -31,6 +31,39 @@ def _log(name, err, ref, bar):
                                 ratio=(err / ref if ref > 0 else 0.0), bar=bar)) + "\n")
 
 
+def _log_fields(**fields):
+    path = os.environ.get("NGNN_GRAD_LOG")
+    if not path:
+        return
+    test = os.environ.get("PYTEST_CURRENT_TEST", "?").split(" ")[0]
+    with open(path, "a") as f:
+        f.write(json.dumps(dict(test=test, **fields)) + "\n")
+
+
+def assert_measured_bar(ours, base, want, msg="", factor=4.0):
+    """A measured bar (tests/test_optim_edges_gpu.py): `ours` may be as far
+    from the float64 `want` as `factor` times what an accepted fp32
+    implementation (`base`) is, with half an fp32 ulp of the tensor's largest
+    value as the floor of that yardstick:
+
+        e_ours <= factor * max(e_base, 2^-24 * max|want|),  e = max|. - want|
+
+    Returns (e_ours, e_base, floor); the caller logs what it keeps of them
+    (_log_fields, NGNN_GRAD_LOG)."""
+    want = want.detach().double().cpu()
+    if want.numel() == 0:
+        return 0.0, 0.0, 0.0
+    ours = ours.detach().double().cpu().reshape(want.shape)
+    base = base.detach().double().cpu().reshape(want.shape)
+    e_ours = float((ours - want).abs().max())
+    e_base = float((base - want).abs().max())
+    floor = 2.0 ** -24 * float(want.abs().max())
+    assert torch.isfinite(ours).all(), f"{msg}: non-finite value"
+    assert e_ours <= factor * max(e_base, floor), (
+        f"{msg}: e_ours {e_ours:.3e} > {factor:g} * max(e_torch {e_base:.3e}, floor {floor:.3e})")
+    return e_ours, e_base, floor
+
+
 def grad_ratio(got, want):
     """max|got - want| / max|want| (float64), and its parts."""
     got = got.detach().double().cpu()
