@@ -42,6 +42,10 @@ __device__ __forceinline__ int wgrad_slices(int R, int S) {
     return max(1, min(S, (R + WG_BM - 1) / WG_BM));
 }
 
+__device__ __forceinline__ float bf16_bits_to_f32(short b) {
+    return __int_as_float(static_cast<int>(static_cast<uint32_t>(static_cast<uint16_t>(b)) << 16));
+}
+
 // One 64-row chunk of one operand, COLS columns wide, held in registers by
 // the 512 threads of a workgroup (a fixed number of loads per thread), so the
 // next chunk's loads are in flight while the MFMAs of this one run.  Loads go
@@ -101,9 +105,9 @@ struct Chunk {  // BF: the operand is bf16 (widened exactly when loaded); MASK: 
             }
             if constexpr (BF && VEC) {
                 raw[u] = buf_load2i(rs, vo, 0, 0);
-            } else if constexpr (BF) {  // the dword holding the element, then its half
-                const int w = buf_load1i(rs, vo & ~3, 0, 0);
-                v[u] = __int_as_float((vo & 2) ? (w & static_cast<int>(0xffff0000u)) : (w << 16));
+            } else if constexpr (BF) {  // a 2-B load: the dword holding the range's last
+                                        // element can end past the range (read as 0)
+                v[u] = bf16_bits_to_f32(buf_load1h(rs, vo, 0, 0));
             } else if constexpr (VEC) {
                 if (!kok || k + 4 <= K) {
                     v[u] = buf_load4(rs, vo, 0, 0);
@@ -120,8 +124,7 @@ struct Chunk {  // BF: the operand is bf16 (widened exactly when loaded); MASK: 
                 if constexpr (MASK == 2 && VEC) {
                     mraw[u] = buf_load2i(rm, mo, 0, 0);
                 } else if constexpr (MASK == 2) {
-                    const int w = buf_load1i(rm, mo & ~3, 0, 0);
-                    mh[u] = __int_as_float((mo & 2) ? (w & static_cast<int>(0xffff0000u)) : (w << 16));
+                    mh[u] = bf16_bits_to_f32(buf_load1h(rm, mo, 0, 0));
                 } else if constexpr (VEC) {
                     m[u] = buf_load4(rm, mo, 0, 0);
                 } else {
@@ -882,7 +885,13 @@ __global__ __launch_bounds__(256) void k_dgrad_fused(
             const int f = f0 + lane;
             const bool act = f < K;
             const int fc = act ? f : 0;
-            float ar = 0.0f, al = 0.0f;
+            // four interleaved partial sums per product (one per component of
+            // the dz quad), added pairwise at the end: a single chain of Fo
+            // dependent fp32 adds missed the input-gradient tolerance at
+            // Fo = 512 (tests/test_layer_bwd_gpu.py::test_dgrad_fused); the
+            // time is the same (profiles/layer_bwd_dgrad_fused_ab.txt)
+            float ar0 = 0.0f, ar1 = 0.0f, ar2 = 0.0f, ar3 = 0.0f;
+            float al0 = 0.0f, al1 = 0.0f, al2 = 0.0f, al3 = 0.0f;
             int n = 0;
             for (; n + 4 <= Fo; n += 4) {
                 const float4 zz = *reinterpret_cast<const float4 *>(z + n);  // uniform: broadcast
@@ -890,9 +899,10 @@ __global__ __launch_bounds__(256) void k_dgrad_fused(
                 const float r2 = wr[(int64_t)(n + 2) * K + fc], r3 = wr[(int64_t)(n + 3) * K + fc];
                 const float l0 = wl[(int64_t)(n + 0) * K + fc], l1 = wl[(int64_t)(n + 1) * K + fc];
                 const float l2 = wl[(int64_t)(n + 2) * K + fc], l3 = wl[(int64_t)(n + 3) * K + fc];
-                ar += zz.x * r0; ar += zz.y * r1; ar += zz.z * r2; ar += zz.w * r3;
-                al += zz.x * l0; al += zz.y * l1; al += zz.z * l2; al += zz.w * l3;
+                ar0 += zz.x * r0; ar1 += zz.y * r1; ar2 += zz.z * r2; ar3 += zz.w * r3;
+                al0 += zz.x * l0; al1 += zz.y * l1; al2 += zz.z * l2; al3 += zz.w * l3;
             }
+            float ar = (ar0 + ar1) + (ar2 + ar3), al = (al0 + al1) + (al2 + al3);
             for (; n < Fo; ++n) {
                 const float zn = z[n];
                 ar += zn * wr[(int64_t)n * K + fc];
