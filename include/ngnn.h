@@ -847,6 +847,54 @@ int ngnn_node_noise_bwd(const float *g, int64_t ldg, const float *x, int64_t ldx
                         int64_t F, float rate, int flags, float *dnoise, int64_t ldd, int32_t *bad,
                         void *stream);
 
+/* ------------------------------------------- similarity top-k edge rewiring
+ * Added within ABI 22 (new entries only: nothing existing changed, so the
+ * version did not move).  topk_rewire(h, edge_index, k_percent,
+ * directed=False) of src/utils/augmentation.py:36-86 without any N x N
+ * matrix.  h: fp32 [n, ldh], F columns used; src / dst: the two rows of
+ * edge_index (int64 [e] each; duplicates collapse, self-loops count);
+ * k2 = 2 * int(n * k_percent), computed by the caller.  With hn = h / max(
+ * ||h||_2, 1e-12) per row (a zero row stays zero), S = hn hn^T clamped to
+ * [-1, 1], A the edge set and D the diagonal, four selections of exactly k2
+ * of the n * n entries each:
+ *   1  k2 smallest of  S * (A and not D ? 1 : 1000)
+ *   2  k2 largest  of  S - 100 [A and not selected by 1] - 100 [D]
+ *   3  k2 largest  of  S * ([A] - 1000 [D])
+ *   4  k2 smallest of  S * ((A ? 1000 : 1) + 1000 [D])
+ * equal keys in ascending flat index i * n + j (-0 equals +0; selection 2
+ * orders by penalty, then S: exactly, not through the rounding of S - 100);
+ * pos = (A minus sel 1) or sel 2, neg = (A minus sel 3) or sel 4, each
+ * written as int64 [2, cap] rows (row 0 at pos, row 1 at pos + pos_cap),
+ * sorted by (row, column) without duplicates -- torch.nonzero's order.
+ * counts (device int32 [3]): {entries of pos, entries of neg, overflow}; an
+ * output longer than its capacity is cut at the capacity (its count is not),
+ * e + k2 always suffices.  overflow = 1: a candidate list filled up (more
+ * than 2^20 non-edges share, to within an fp32 step or two, the similarity
+ * at a selection's threshold -- a mass tie): nothing was written out of
+ * bounds, the outputs are not valid.
+ * bad (device int32, nullable): incremented once per edge with an endpoint
+ * outside [0, n); such an edge is otherwise ignored.
+ * sel_out (nullable): int64 [4, k2], the four selections' flat indices in
+ * selection order (best key first).
+ * S is exact fp32 (v_mfma_f32_16x16x4_f32 over the non-edges, fp32 FMAs over
+ * the edges and the diagonal); results are bitwise reproducible.
+ * ws: ngnn_topk_rewire_workspace_bytes(n, F, e, k2) bytes, 256-B aligned:
+ * O(n F + e + k2) plus the bounded candidate lists; 0 for n == 0 or sizes
+ * the entry refuses.  Nothing is allocated and the host does not wait.
+ * n == 0: success, nothing is read or written.  Before any launch: a
+ * negative size or capacity, a NULL h / src / dst / pos / neg (where its
+ * size is not 0) / counts / ws: NGNN_E_ARG; ldh < F: NGNN_E_SHAPE;
+ * n > 65535 (a flat index fits 32 bits), k2 > n * n, e or k2 > 2^29,
+ * F > 2^20, a capacity >= 2^31: NGNN_E_RANGE; a misaligned ws / pos / neg:
+ * NGNN_E_ALIGN; ws_bytes too small: NGNN_E_WORKSPACE.
+ * Replaces F.normalize, the dense similarity matrix, the dense masks, four
+ * torch.topk over n * n keys and two torch.nonzero [ext: torch]. */
+size_t ngnn_topk_rewire_workspace_bytes(int64_t n, int64_t F, int64_t e, int64_t k2);
+int ngnn_topk_rewire(const float *h, int64_t ldh, int64_t n, int64_t F, const int64_t *src,
+                     const int64_t *dst, int64_t e, int64_t k2, int64_t *pos, int64_t pos_cap,
+                     int64_t *neg, int64_t neg_cap, int32_t *counts, int32_t *bad, int64_t *sel_out,
+                     void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -122,6 +122,10 @@ SIGNATURES = {
                                    _i64, _p, _p]),
     "ngnn_node_noise_bwd": (_int, [_p, _i64, _p, _i64, _p, _i64, _i64, _p, _int, _i64, _i64,
                                    ctypes.c_float, _int, _p, _i64, _p, _p]),
+    # (added within ABI 22: similarity top-k edge rewiring)
+    "ngnn_topk_rewire_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
+    "ngnn_topk_rewire": (_int, [_p, _i64, _i64, _i64, _p, _p, _i64, _i64, _p, _i64, _p, _i64, _p, _p, _p,
+                                _p, _sz, _p]),
 }
 
 _lib = None

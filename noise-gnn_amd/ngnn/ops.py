@@ -234,3 +234,103 @@ def add_node_noise(x: torch.Tensor, noise: torch.Tensor, n_id: torch.Tensor | No
             raise ValueError("add_node_noise: n_id must be an int64 CUDA tensor with one id per row of x")
         n_id = n_id.contiguous()
     return _AddNodeNoise.apply(x, noise, n_id, float(rate), bool(sign))
+
+
+# ---- similarity top-k edge rewiring (ngnn_topk_rewire) ----
+
+_bad_endpoint_counters: dict = {}  # device index -> int32[1] on that device
+
+
+def _bad_endpoint_counter(device: torch.device) -> torch.Tensor:
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    c = _bad_endpoint_counters.get(idx)
+    if c is None:
+        c = _bad_endpoint_counters[idx] = torch.zeros(1, dtype=torch.int32, device=torch.device("cuda", idx))
+    return c
+
+
+def rewire_bad_endpoints(device=None, reset: bool = False) -> int:
+    """How many edges ``topk_rewire`` met on ``device`` with an endpoint
+    outside ``[0, N)`` (they are ignored).  Debugging only: reading the device
+    counter synchronises."""
+    c = _bad_endpoint_counter(torch.device("cuda" if device is None else device))
+    n = int(c.item())
+    if reset:
+        c.zero_()
+    return n
+
+
+def topk_rewire(h: torch.Tensor, edge_index: torch.Tensor, device=None, k_percent: float = 0.1,
+                directed: bool = False, *, return_selections: bool = False):
+    """The reference's ``topk_rewire(h, edge_index, device, k_percent,
+    directed=False)`` (``src/utils/augmentation.py:36-86``) -> ``(pos_edge,
+    neg_edge)``, contiguous int64 ``[2, M]`` on ``h``'s device, sorted by (row,
+    column) without duplicates as ``torch.nonzero`` lists them -- with no
+    ``N x N`` tensor anywhere: the cosine similarities are computed tile by
+    tile on the matrix cores and selected as they come (``ngnn_topk_rewire``).
+
+    With ``k2 = 2 * int(N * k_percent)``: the ``k2`` least similar entries by
+    the reference's key leave the positive graph and the ``k2`` most similar
+    non-edges join it; the ``k2`` most similar edges leave the negative graph
+    and the ``k2`` least similar entries join it (the keys, quirks included:
+    include/ngnn.h).  Equal keys are taken in ascending flat index ``i * N +
+    j``; the result is bitwise reproducible.  ``h`` is detached (the
+    reference's result carries no gradient); ``device`` is accepted for the
+    reference's signature and ignored.  One host read (the two output
+    lengths), where ``torch.nonzero`` synchronises in the reference.
+
+    ``return_selections=True`` also returns the four selections' flat indices
+    (int64 ``[4, k2]``, best key first).  ``directed=True`` is refused (the
+    reference's branch raises ``UnboundLocalError``).  fp32, GPU only,
+    ``N <= 65535``; an edge with an endpoint outside ``[0, N)`` is ignored and
+    counted (``rewire_bad_endpoints``)."""
+    if directed:
+        raise NotImplementedError("topk_rewire: directed=True returns nothing in the reference "
+                                  "(UnboundLocalError); only directed=False is implemented")
+    if not isinstance(h, torch.Tensor) or not h.is_cuda:
+        raise RuntimeError("ngnn runs on the GPU only: topk_rewire's h is on the CPU")
+    if h.dim() != 2:
+        raise ValueError(f"topk_rewire: h must be 2-D [N, F], got shape {tuple(h.shape)}")
+    if h.dtype != torch.float32:
+        raise TypeError(f"topk_rewire: only float32 h is supported, got {h.dtype}")
+    if not isinstance(edge_index, torch.Tensor) or edge_index.dim() != 2 or edge_index.size(0) != 2 \
+            or edge_index.dtype != torch.int64:
+        raise ValueError("topk_rewire: edge_index must be an int64 tensor of shape [2, E]")
+    dev = h.device
+    hs = _row_major(h.detach())
+    ei = edge_index.to(dev).contiguous()
+    N, F = hs.shape
+    E = ei.size(1)
+    k2 = 2 * int(N * k_percent)
+    if k2 < 0:
+        raise ValueError(f"topk_rewire: k_percent must not be negative, got {k_percent}")
+    lib = _lib.load()
+    cap = E + k2
+    if N == 0:
+        empty = torch.empty(2, 0, dtype=torch.int64, device=dev)
+        sel = torch.empty(4, 0, dtype=torch.int64, device=dev)
+        return (empty, empty.clone(), sel) if return_selections else (empty, empty.clone())
+    ws_bytes = lib.ngnn_topk_rewire_workspace_bytes(N, F, E, k2)
+    ws = pos = neg = counts = sel = None
+    if ws_bytes:  # (0: sizes the entry refuses -- it reports which, before anything is read)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        pos = torch.empty(2, cap, dtype=torch.int64, device=dev)
+        neg = torch.empty(2, cap, dtype=torch.int64, device=dev)
+        counts = torch.zeros(3, dtype=torch.int32, device=dev)
+        if return_selections:
+            sel = torch.empty(4, k2, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        bad = _bad_endpoint_counter(dev) if ws_bytes else None
+        # algorithmic bytes: h once, the edges, the outputs (the similarity tiles stay on chip)
+        with _timing.span("topk_rewire", N * F * 4 + E * 16 + 2 * cap * 16):
+            rc = lib.ngnn_topk_rewire(
+                _lib.ptr(hs), _ld(hs), N, F, _lib.ptr(ei[0]) if E else None, _lib.ptr(ei[1]) if E else None,
+                E, k2, _lib.ptr(pos), cap, _lib.ptr(neg), cap, _lib.ptr(counts), _lib.ptr(bad),
+                _lib.ptr(sel), _lib.ptr(ws), ws_bytes, _lib.stream_handle(dev))
+    _lib.check(rc, "ngnn_topk_rewire")
+    n_pos, n_neg, overflow = counts.tolist()
+    if overflow:
+        raise _lib.NGNNError("topk_rewire: a candidate list filled up -- more than 2^20 entries tie at the "
+                             "similarity of a selection's threshold (include/ngnn.h)")
+    out = (pos[:, :n_pos].contiguous(), neg[:, :n_neg].contiguous())
+    return out + (sel,) if return_selections else out
