@@ -227,42 +227,73 @@ inline Dropout make_dropout(float p, uint64_t seed) {
     return d;
 }
 
+// One per-layer forward call: ngnn_sage_fwd_raw's arguments with the flag bits
+// of `reduce` decoded, as sage_fwd_rowtile, sage_fwd_wide and
+// sage_wide_aggregate take them (each reads the members it needs).
+struct LayerFwd {
+    // input rows: x (or the device word x_dev holding its address), ldx in
+    // elements; xrow / xrow_dev: the fused x[n_id] gather over an x_rows-row
+    // table, col_x the neighbour ids already mapped through it
+    const float *x = nullptr;
+    const float *const *x_dev = nullptr;
+    const int64_t *xrow = nullptr;
+    const int64_t *const *xrow_dev = nullptr;
+    const int32_t *col_x = nullptr;
+    int64_t x_rows = 0, ldx = 0, K = 0, Fo = 0, n_rows = 0;
+    int64_t n_edge_rows = -1;  // rows with in-edges come first, below this (-1: unknown)
+    const int32_t *n_rows_dev = nullptr, *n_edge_rows_dev = nullptr, *rowptr = nullptr, *col = nullptr;
+    int reduce = NGNN_REDUCE_SUM;  // NGNN_REDUCE_* alone (no flag bits)
+    // raw PyG Linear rows [Fo, K] with row stride ldw, or (ldw == 0) packed
+    // fragments; wr null: no root term, wl null: no neighbour term
+    const void *wl = nullptr, *wr = nullptr;
+    const float *bias = nullptr;
+    float *out = nullptr;
+    float *agg_out = nullptr;  // the saved aggregate (the backward's input)
+    float *z = nullptr;        // narrow mode: z = x W_l^T [n_rows, ldz]
+    int64_t ldw = 0, ldo = 0, ld_agg = 0, ldz = 0;
+    int relu = 0;
+    float p_drop = 0.0f;
+    uint64_t seed = 0;
+    const uint64_t *seed_dev = nullptr;
+    void *ws = nullptr;  // a streamed W_l's packed form (row-tile); aggregate + weight image (wide)
+    size_t ws_bytes = 0;
+    void *img_ws = nullptr;  // kImgWsBytes for a slice's prebuilt X3 root image
+    bool exact = true;       // root term on fp32 MFMA (else the 3 x bf16 split, raw weights only)
+    bool x_bf16 = false, w_bf16 = false, out_bf16 = false;  // NGNN_X_BF16, NGNN_W_BF16, NGNN_OUT_BF16
+    bool wl_prepacked = false;  // NGNN_WL_PREPACKED: ws already holds ngnn_pack_weight(wl)
+    bool agg_pre = false;       // agg_out already holds the aggregate (sage_wide_aggregate)
+};
+
 // Row-tile forward (ngnn_sage_rt.hip): returns 1 (launch status in *rc) when
-// it takes the call, 0 when the shape is outside its envelope.  exact: root
-// term on fp32 MFMA (else the 3 x bf16 split when the weights are raw rows).
-int sage_fwd_rowtile(const float *x, int64_t ldx, int64_t K, int64_t n_rows,
-                     const int32_t *n_rows_dev, const int32_t *rowptr, const int32_t *col,
-                     int reduce, const void *wl_packed, const void *wr_packed, const float *bias,
-                     int64_t Fo, float *out, int64_t ldo, int relu, float p_drop, uint64_t seed,
-                     const uint64_t *seed_dev, float *agg_out, int64_t ld_agg, hipStream_t st,
-                     int *rc, int64_t ldw = 0, void *wl_ws = nullptr, size_t wl_ws_bytes = 0,
-                     const float *const *x_dev = nullptr, bool exact = true,
-                     float *z = nullptr, int64_t ldz = 0, const int64_t *xrow = nullptr,
-                     const int64_t *const *xrow_dev = nullptr, int64_t x_rows = 0,
-                     const int32_t *col_x = nullptr, bool x_bf16 = false,
-                     bool w_bf16 = false, bool wl_prepacked = false, bool agg_pre = false,
-                     bool out_bf16 = false, int64_t n_edge_rows = -1,
-                     const int32_t *n_edge_rows_dev = nullptr, void *img_ws = nullptr);
+// it takes the call, 0 when the shape is outside its envelope.
+int sage_fwd_rowtile(const LayerFwd &L, hipStream_t st, int *rc);
 // the tail of ngnn_sage_fwd_raw's workspace that holds a slice's prebuilt
 // X3 root image (ngnn_root.hip: k_x3_image)
 constexpr size_t kImgWsBytes = 160 * 1024;
+
+// The row-tile kernel's LDS envelope -- the one copy of it (ngnn_sage_rt.hip;
+// fused.pad_k_ok restates its split-bf16 case in Python).  One m-tile (16
+// outputs) of the root image is, in the X3 layout, C bf16 chunks of 32
+// columns in 3 parts (1 with w1) of 1 KiB + T4 <= X3_TAIL_MAX fp32 steps of
+// 4 columns (a longer tail becomes one zero-padded chunk: kpad); else, and for
+// W_l, one fp32 fragment set over all of K.  ntw_max: the widest column slice
+// in m-tiles, the first of {16, 8, 6, 4, 3, 2} <= max_ntw whose image fits
+// kRtLdsCap (0: none does).  max_ntw: sage_fwd_rowtile passes the A/B build
+// flag NGNN_RT_MAXNTW, the routing query sage_wide_preferred does not (16).
+constexpr size_t kRtLdsCap = 160 * 1024 - 1024 - 256;  // minus the bias slice and static LDS
+struct RtImage {
+    int C, T4, kpad;
+    size_t frag_kb, root_kb;  // bytes per m-tile: fp32 fragments / the root image
+    int ntw_max;
+};
+RtImage rt_root_image(int64_t K, bool x3, bool w1, bool no_root, int max_ntw);
 
 // Wide-layer forward (ngnn_wide.hip): an aggregate launch into agg_out (or
 // the workspace) + a 2-D tiled fp32-MFMA dual GEMM.  Raw [F_out, K] weights.
 bool sage_wide_preferred(int64_t K, int64_t Fo, bool exact);
 size_t sage_wide_workspace_bytes(int64_t K, int64_t n_rows);
 size_t wide_wimg_bytes(int64_t K, int64_t Fo);  // the split-bf16 weight image (at the workspace's tail)
-int sage_wide_aggregate(const float *x, int64_t ldx, int64_t K, int64_t n_rows,
-                        const int32_t *n_rows_dev, int64_t n_edge_rows,
-                        const int32_t *n_edge_rows_dev, const int32_t *rowptr, const int32_t *col,
-                        int reduce, float *agg, int64_t ld_agg, hipStream_t st,
-                        const float *const *x_dev = nullptr);
-int sage_fwd_wide(const float *x, int64_t ldx, int64_t K, int64_t n_rows,
-                  const int32_t *n_rows_dev, int64_t n_edge_rows, const int32_t *n_edge_rows_dev,
-                  const int32_t *rowptr, const int32_t *col, int reduce, const float *wl,
-                  const float *wr, int64_t ldw, const float *bias, int64_t Fo, float *out,
-                  int64_t ldo, int relu, float p_drop, uint64_t seed, const uint64_t *seed_dev,
-                  float *agg_out, int64_t ld_agg, void *ws, size_t ws_bytes, hipStream_t st,
-                  bool exact = false, const float *const *x_dev = nullptr);
+int sage_wide_aggregate(const LayerFwd &L, hipStream_t st);
+int sage_fwd_wide(const LayerFwd &L, hipStream_t st);
 
 }  // namespace ngnn

@@ -476,11 +476,13 @@ extern "C" int ngnn_sage_fwd(const float *x, int64_t ldx, int64_t K, int64_t n_r
     if (n_rows == 0) return NGNN_OK;
     NGNN_RETURN_IF(!x || !out, NGNN_E_ARG);
     if (!xmask) {  // default path: the row-tile kernel (ngnn_sage_rt.hip)
+        LayerFwd L;  // packed weights (ldw 0): exact fp32 MFMA, every row may have in-edges
+        L.x = x, L.ldx = ldx, L.K = K, L.Fo = Fo, L.n_rows = n_rows, L.n_rows_dev = n_rows_dev;
+        L.rowptr = rowptr, L.col = col, L.reduce = reduce, L.wl = wl_packed, L.wr = wr_packed, L.bias = bias;
+        L.out = out, L.ldo = ldo, L.relu = relu, L.p_drop = p_drop, L.seed = seed, L.seed_dev = seed_dev;
+        L.agg_out = agg_out, L.ld_agg = ld_agg;
         int rc = NGNN_OK;
-        if (sage_fwd_rowtile(x, ldx, K, n_rows, n_rows_dev, rowptr, col, reduce, wl_packed,
-                             wr_packed, bias, Fo, out, ldo, relu, p_drop, seed, seed_dev, agg_out,
-                             ld_agg, as_stream(stream), &rc))
-            return rc;
+        if (sage_fwd_rowtile(L, as_stream(stream), &rc)) return rc;
     }
     const int vec_in = (K % 4 == 0) && (ldx % 4 == 0) && aligned(x, 16) &&
                        (!xmask || ((ldm % 4 == 0) && aligned(xmask, 16)));

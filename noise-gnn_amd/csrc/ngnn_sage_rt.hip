@@ -505,242 +505,267 @@ int narrow_agg_launch(const float *z, int64_t ldz, int64_t Fo, const int32_t *ro
     return launch_status();
 }
 
+// The row-tile kernel's LDS envelope (declared in ngnn_device.h)
+RtImage rt_root_image(int64_t K, bool x3, bool w1, bool no_root, int max_ntw) {
+    RtImage im{};
+    im.C = static_cast<int>(K / 32);
+    im.T4 = static_cast<int>(ceil_div(K % 32, 4));
+    if (im.T4 > X3_TAIL_MAX) {
+        im.C += 1;
+        im.T4 = 0;
+        im.kpad = 1;
+    }
+    // (no root term: the X3 layout with an empty image -- no MFMAs, no LDS)
+    if (no_root) im.C = im.T4 = im.kpad = 0;
+    im.frag_kb = static_cast<size_t>(ceil_div(K, 16)) * 64 * sizeof(v4f);
+    im.root_kb = x3 ? (static_cast<size_t>((w1 ? 1 : 3) * im.C) * 64 * 16 + static_cast<size_t>(im.T4) * 64 * 4)
+                    : im.frag_kb;
+    // (no root term: the slice width is set by the W_l image alone)
+    const size_t img_kb = no_root ? im.frag_kb : im.root_kb;
+    for (int c : {16, 8, 6, 4, 3, 2})
+        if (c <= max_ntw && static_cast<size_t>(c) * img_kb <= kRtLdsCap) {
+            im.ntw_max = c;
+            break;
+        }
+    return im;
+}
+
+namespace {
+
+// ---- sage_fwd_rowtile's steps: plan, per-slice W_l staging, launch.  The
+// plan: a layer's form and its column slicing -- outputs wider than one slice
+// (<= 256 columns, fewer when K is large) run as one launch per slice.
+struct RtPlan {
+    bool x3;  // root term in the X3 layout (3 x bf16 split; also "no root term")
+    bool w1;  // bf16-exact weights (NGNN_W_BF16): a one-part image (MEAN / SUM kernels)
+    bool narrow, no_root;
+    int KG;
+    RtImage im;
+    int64_t slice;  // output columns per launch
+};
+
+// false: outside the envelope.  raw: PyG Linear rows (ldw > 0), else packed
+// fragments.  narrow: one launch computes [x W_r^T | x W_l^T] (2 NT1 tiles),
+// no column slicing -- both halves in one image.
+bool rt_plan(int64_t K, int64_t Fo, bool raw, bool exact, bool w_bf16, int reduce, bool narrow, bool no_root,
+             RtPlan &p) {
+    p.x3 = (!exact && raw) || no_root;
+    p.w1 = w_bf16 && p.x3 && !no_root && reduce != NGNN_REDUCE_MAX;
+    p.narrow = narrow;
+    p.no_root = no_root;
+    p.KG = static_cast<int>(ceil_div(K, 16));
+    p.im = rt_root_image(K, p.x3, p.w1, no_root, NGNN_RT_MAXNTW);
+    if (p.im.ntw_max == 0 || (narrow && 2 * ceil_div(Fo, 16) > p.im.ntw_max)) return false;
+    p.slice = narrow ? Fo : 16 * static_cast<int64_t>(p.im.ntw_max);
+    return true;
+}
+
+// One column slice of Fo_c outputs: its tiles, the kernel instantiation and
+// the dynamic LDS.  W_l (fp32) shares the LDS when both fit (wl_lds);
+// otherwise its fragments stream from L2 (stage_wl).
+struct RtSlice {
+    int NT1, NT, NTW;
+    bool wl_lds;
+    size_t lds;
+};
+
+RtSlice rt_slice(const RtPlan &p, int64_t Fo_c, bool has_l) {
+    RtSlice s;
+    s.NT1 = static_cast<int>(ceil_div(Fo_c, 16));
+    s.NT = p.narrow ? 2 * s.NT1 : s.NT1;
+    s.NTW = s.NT <= 2 ? 2 : s.NT <= 3 ? 3 : s.NT <= 4 ? 4 : s.NT <= 6 ? 6 : s.NT <= 8 ? 8 : 16;
+    const size_t rbytes = static_cast<size_t>(s.NTW) * p.im.root_kb;
+    const size_t wbytes = static_cast<size_t>(s.NTW) * p.im.frag_kb;
+    const size_t bbytes = static_cast<size_t>(s.NTW) * 16 * sizeof(float);
+    s.wl_lds = has_l && rbytes + wbytes + bbytes <= kRtLdsCap + 1024;
+    s.lds = rbytes + (s.wl_lds ? wbytes : 0) + bbytes;
+    return s;
+}
+
+// The launch arguments of column slice [c0, c0 + Fo_c), but for a streamed
+// W_l (stage_wl) and the prebuilt root image (build_image).
+// (RtArgs::tile_end_dev is dead -- null, never read; removing it moves the
+// later kernel arguments: for a change that re-measures)
+RtArgs slice_args(const LayerFwd &L, const RtPlan &p, const RtSlice &s, int64_t c0, int64_t Fo_c, bool has_l,
+                  const Dropout &drop) {
+    RtArgs a{};
+    a.x = L.x;
+    a.ldx = L.ldx;
+    a.K = static_cast<int>(L.K);
+    a.KG = p.KG;
+    a.n_rows = static_cast<int>(L.n_rows);
+    a.n_rows_dev = L.n_rows_dev;
+    a.rowptr = L.rowptr;
+    a.col = L.col;
+    // a slice's weights: packed fragments are n-tile major (contiguous
+    // sub-array); raw weights are rows [c0, c0 + Fo_c)
+    const int64_t woff = L.ldw ? c0 * L.ldw / 4 : (c0 / 16) * p.KG * 64;
+    a.wl = has_l ? static_cast<const v4f *>(L.wl) + woff : nullptr;
+    a.wr = p.no_root ? nullptr : static_cast<const v4f *>(L.wr) + woff;
+    a.wr_raw = (L.ldw && !p.no_root) ? static_cast<const float *>(L.wr) + c0 * L.ldw : nullptr;
+    a.ldw = L.ldw;
+    a.C = p.im.C;
+    a.T4 = p.im.T4;
+    a.kpad = p.im.kpad;
+    a.wlb_fo = static_cast<int>(L.Fo);
+    a.CL = static_cast<int>(ceil_div(L.K, 32));
+    a.NT = s.NT;
+    a.NT1 = s.NT1;
+    // (unknown: every row may have in-edges -- no root-only phase)
+    a.n_edge = static_cast<int>(L.n_edge_rows < 0 ? L.n_rows : std::min(L.n_edge_rows, L.n_rows));
+    a.n_edge_dev = L.n_edge_rows_dev;
+    a.wz_raw = p.narrow ? static_cast<const float *>(L.wl) : nullptr;
+    a.z = L.z;
+    a.ldz = L.ldz;
+    a.Fo = static_cast<int>(Fo_c);
+    a.out = L.out_bf16 ? reinterpret_cast<float *>(reinterpret_cast<uint16_t *>(L.out) + c0) : L.out + c0;
+    a.ldo = L.ldo;
+    a.vec_out = (Fo_c % 4 == 0) && (L.ldo % 4 == 0) && aligned(a.out, L.out_bf16 ? 8 : 16);
+    a.out_bf16 = L.out_bf16;
+    a.agg_out = (c0 == 0 && !p.narrow && !L.agg_pre) ? L.agg_out : nullptr;
+    a.ld_agg = L.ld_agg;
+    // later column slices read the aggregate the first one saved (the
+    // launches are stream-ordered) instead of gathering it again; agg_pre:
+    // every slice reads it (written by a separate aggregate launch)
+    a.agg_in = ((c0 > 0 || L.agg_pre) && !p.narrow && has_l) ? L.agg_out : nullptr;
+    a.epi = Epi{L.bias ? L.bias + c0 : nullptr, L.relu, drop, static_cast<int>(c0)};
+    a.seed_dev = L.seed_dev;
+    a.x_dev = L.x_dev;
+    a.xrow = L.xrow;
+    a.xrow_dev = L.xrow_dev;
+    a.x_rows = L.x_rows;
+    a.col_x = (L.xrow || L.xrow_dev) ? L.col_x : nullptr;
+    a.x_bf16 = L.x_bf16;
+    a.w1 = p.w1;
+    return a;
+}
+
+// W_l of slice c0 streamed from L2 (it does not fit the LDS beside the root
+// image) out of the caller's workspace, packed there once, with the first
+// slice: as fp32 fragments (ngnn_pack_weight's layout; NGNN_WL_PREPACKED: the
+// producer keeps them current), or for one-part (bf16-exact) layers as the
+// bf16 image behind them -- the neighbour term on bf16 MFMA, no fp32 pack.
+// img_pre: the root image's own launch (build_image) packs W_l too, handed
+// a.wlp_* / a.wlb_src, instead of a pack launch here.  Returns a workspace or
+// launch error.
+int stage_wl(const LayerFwd &L, const RtPlan &p, int64_t c0, bool img_pre, RtArgs &a, hipStream_t st) {
+    const int64_t K = L.K, Fo = L.Fo;
+    const float *wl = static_cast<const float *>(L.wl);
+    if (L.ldw) {  // (packed weights stream as they are)
+        if (c0 == 0 && !p.w1) {
+            if (!L.ws || L.ws_bytes < ngnn_pack_weight_bytes(Fo, K)) return NGNN_E_WORKSPACE;
+            if (img_pre && !L.wl_prepacked) {
+                a.wlp_src = wl;
+                a.wlp_dst = static_cast<v4f *>(L.ws);
+                a.wlp_fo = static_cast<int>(Fo);
+            } else if (!L.wl_prepacked) {
+                const int rc = ngnn_pack_weight(wl, L.ldw, Fo, K, L.ws, st);
+                if (rc) return rc;
+            }
+        }
+        a.wl = static_cast<const v4f *>(L.ws) + (c0 / 16) * p.KG * 64;
+    }
+    if (p.w1) {
+        if (!L.ldw || !L.ws || L.ws_bytes < ngnn_pack_weight_bytes(Fo, K) + wl_b16_bytes(Fo, K))
+            return NGNN_E_WORKSPACE;
+        uint16_t *img16 = reinterpret_cast<uint16_t *>(static_cast<char *>(L.ws) + ngnn_pack_weight_bytes(Fo, K));
+        if (c0 == 0 && img_pre) {
+            a.wlb_src = wl;
+        } else if (c0 == 0) {
+            const int NTa = static_cast<int>(ceil_div(Fo, 16));
+            const int64_t total = static_cast<int64_t>(NTa) * a.CL * 512;
+            hipLaunchKernelGGL(k_pack_wl_b16, dim3(static_cast<unsigned>(ceil_div(total, 256))), dim3(256), 0, st,
+                               wl, L.ldw, static_cast<int>(Fo), static_cast<int>(K), a.CL, NTa, img16);
+            const int rc = launch_status();
+            if (rc) return rc;
+        }
+        a.wlb = img16 + (c0 / 16) * a.CL * 64 * 8;
+    }
+    return NGNN_OK;
+}
+
+// One slice's launches: k_sage_rt over all its tiles, or -- when a k_root
+// instantiation (ngnn_root.hip) covers this layer -- k_sage_rt on the tiles
+// with in-edges (none in narrow mode), then k_root on the tiles past the
+// edge-row bound.
+int launch_slice(RtArgs &a, const RtPlan &p, const RtSlice &s, int reduce, int n_tiles, hipStream_t st) {
+    const bool vec = a.vec_out && (a.Fo == a.NT * 16);
+    const int form = (p.x3 && !NGNN_RT_STATIC && !p.no_root) ? rt_form(a, s.NTW, vec) : 0;
+    // policy (NGNN_ROOT, read once): 1 (default) k_root for layers with no
+    // in-kernel neighbour term (narrow mode: every tile); 2 also split the
+    // layers with edge tiles (k_sage_rt edge tiles, then k_root -- measured
+    // slower on products layer 0: the edge tiles alone then hold the GPU
+    // ~48 us, in one launch they overlap the root tiles); 0 never
+    static const int policy = [] {
+        const char *e = std::getenv("NGNN_ROOT");
+        return e ? std::atoi(e) : 1;
+    }();
+    const bool want_root = policy == 2 || (policy == 1 && !a.wl);
+    if (form && want_root && launch_root(a, s.NTW, form, vec, st, true) == NGNN_OK) {
+        if (a.wl) {
+            a.root_split = 1;
+            const int rc = dispatch_rt(s.NTW, a, reduce, s.wl_lds, p.x3, n_tiles, s.lds, st);
+            if (rc) return rc;
+            a.root_split = 0;
+        }
+        return launch_root(a, s.NTW, form, vec, st);
+    }
+    return dispatch_rt(s.NTW, a, reduce, s.wl_lds, p.x3, n_tiles, s.lds, st);
+}
+
+}  // namespace
+
 // Returns 1 and stores the launch status in *rc when the row-tile kernel
 // takes this call, 0 when the shape is outside its envelope (the caller then
 // runs the 64-row kernel).  Envelope: no input mask, K % 4 == 0 with 16-B
-// aligned rows, the W_r image of one column slice fitting in LDS.  Outputs
-// wider than one slice (<= 256 columns, fewer when K is large) run as one
-// launch per slice; the packed weights are n-tile major, so a slice is a
-// contiguous sub-array.  exact: fp32 MFMA for the root term (else the 3 x
-// bf16 split, raw weights only).
-int sage_fwd_rowtile(const float *x, int64_t ldx, int64_t K, int64_t n_rows,
-                     const int32_t *n_rows_dev, const int32_t *rowptr, const int32_t *col,
-                     int reduce, const void *wl_packed, const void *wr_packed, const float *bias,
-                     int64_t Fo, float *out, int64_t ldo, int relu, float p_drop, uint64_t seed,
-                     const uint64_t *seed_dev, float *agg_out, int64_t ld_agg, hipStream_t st,
-                     int *rc, int64_t ldw, void *wl_ws, size_t wl_ws_bytes,
-                     const float *const *x_dev, bool exact, float *z, int64_t ldz,
-                     const int64_t *xrow, const int64_t *const *xrow_dev, int64_t x_rows,
-                     const int32_t *col_x, bool x_bf16, bool w_bf16, bool wl_prepacked,
-                     bool agg_pre, bool out_bf16, int64_t n_edge_rows,
-                     const int32_t *n_edge_rows_dev, void *img_ws) {
+// aligned rows, the W_r image of one column slice fitting in LDS (rt_plan /
+// rt_root_image).  L.exact: fp32 MFMA for the root term (else the 3 x bf16
+// split, raw weights only).
+int sage_fwd_rowtile(const LayerFwd &L, hipStream_t st, int *rc) {
     // (with x_dev the run-time address must be 16-B aligned, as torch's are)
-    if (K % 4 != 0 || ldx % 4 != 0 || (!x_dev && !aligned(x, 16))) return 0;
-    if (ldw && (ldw % 4 != 0 || !aligned(wr_packed, 16) || (wl_packed && !aligned(wl_packed, 16))))
-        return 0;
-    const bool no_root = wr_packed == nullptr;  // raw weights only (checked by the caller)
-    if (agg_out && (ld_agg % 4 != 0 || !aligned(agg_out, 16))) return 0;
+    if (L.K % 4 != 0 || L.ldx % 4 != 0 || (!L.x_dev && !aligned(L.x, 16))) return 0;
+    if (L.ldw && (L.ldw % 4 != 0 || !aligned(L.wr, 16) || (L.wl && !aligned(L.wl, 16)))) return 0;
+    const bool no_root = L.wr == nullptr;  // raw weights only (checked by the caller)
+    if (L.agg_out && (L.ld_agg % 4 != 0 || !aligned(L.agg_out, 16))) return 0;
     // the gather reads neighbour rows through one resource over all of x
     // (unsigned 32-bit offsets below kOOB); every other operand is addressed
     // per 16-row tile (no size limit)
-    const bool indexed = xrow != nullptr || xrow_dev != nullptr;
+    const bool indexed = L.xrow != nullptr || L.xrow_dev != nullptr;
     // (a graph slot may load materialized batches too: the word then holds 0)
-    const int64_t ebytes = x_bf16 ? 2 : 4;
-    if ((indexed ? std::max(x_rows, n_rows) : n_rows) * ldx * ebytes > kRangeMax || (indexed && x_rows <= 0))
+    const int64_t ebytes = L.x_bf16 ? 2 : 4;
+    if ((indexed ? std::max(L.x_rows, L.n_rows) : L.n_rows) * L.ldx * ebytes > kRangeMax ||
+        (indexed && L.x_rows <= 0))
         return 0;
-    const int KG = static_cast<int>(ceil_div(K, 16));
-    // X3 root term: C bf16 chunks of 32 + T4 fp32 steps of 4 (tails over 12
-    // columns become one zero-padded bf16 chunk)
-    // (no root term: the X3 layout with an empty image -- no MFMAs, no LDS)
-    const bool x3 = (!exact && ldw > 0) || no_root;
+    const bool narrow = L.z != nullptr;
+    RtPlan p;
+    if (!rt_plan(L.K, L.Fo, L.ldw > 0, L.exact, L.w_bf16, L.reduce, narrow, no_root, p)) return 0;
     // bf16 rows: X3 layout only, 8-B aligned rows (ldx a multiple of 4 elements)
-    if (x_bf16 && (!x3 || ldx % 4 != 0)) return 0;
-    // narrow mode: one launch computes [x W_r^T | x W_l^T] (2 NT1 tiles) --
-    // X3 only, no neighbour term, no saved aggregate, no column slicing
-    const bool narrow = z != nullptr;
-    if (narrow && (!x3 || !wl_packed || ldz < ceil_div(Fo, 16) * 16 || ldz % 4 != 0 || !aligned(z, 16)))
+    if (L.x_bf16 && !p.x3) return 0;
+    // narrow mode: X3 only, no neighbour term, no saved aggregate
+    if (narrow && (!p.x3 || !L.wl || L.ldz < ceil_div(L.Fo, 16) * 16 || L.ldz % 4 != 0 || !aligned(L.z, 16)))
         return 0;
-    int C = static_cast<int>(K / 32), T4 = static_cast<int>(ceil_div(K % 32, 4)), kpad = 0;
-    if (T4 > X3_TAIL_MAX) {
-        C += 1;
-        T4 = 0;
-        kpad = 1;
-    }
-    if (no_root) C = T4 = kpad = 0;
-    // bf16-exact weights (NGNN_W_BF16): a one-part image (MEAN / SUM kernels)
-    const bool w1 = w_bf16 && x3 && !no_root && reduce != NGNN_REDUCE_MAX;
     // (development builds hold the fp32 split-bf16 MEAN kernels only)
-    if (NGNN_RT_FAST_BUILD && (!x3 || x_bf16 || w1 || reduce != NGNN_REDUCE_MEAN)) return 0;
-    const size_t frag_kb = static_cast<size_t>(KG) * 64 * sizeof(v4f);  // one fp32 m-tile, all of K
-    // one m-tile of the root image: X3 3 parts (1 with w1) x C chunks x 1 KiB + the tail
-    const size_t root_kb = x3 ? (static_cast<size_t>((w1 ? 1 : 3) * C) * 64 * 16 +
-                                 static_cast<size_t>(T4) * 64 * 4)
-                              : frag_kb;
-    // (no root term: the slice width is set by the W_l image alone)
-    const size_t img_kb = no_root ? frag_kb : root_kb;
-    const size_t lds_cap = 160 * 1024 - 1024 - 256;  // minus the bias slice and static LDS
-    int ntw_max = 0;
-    for (int c : {16, 8, 6, 4, 3, 2})
-        if (c <= NGNN_RT_MAXNTW && static_cast<size_t>(c) * img_kb <= lds_cap) {
-            ntw_max = c;
-            break;
-        }
-    if (ntw_max == 0) return 0;
-    if (narrow && 2 * ceil_div(Fo, 16) > ntw_max) return 0;  // both halves in one image
-    const int64_t slice = narrow ? Fo : 16 * static_cast<int64_t>(ntw_max);
-    const Dropout drop = make_dropout(p_drop, seed);
-    for (int64_t c0 = 0; c0 < Fo; c0 += slice) {
-        const int64_t Fo_c = std::min<int64_t>(slice, Fo - c0);
-        const int NT1 = static_cast<int>(ceil_div(Fo_c, 16));
-        const int NT = narrow ? 2 * NT1 : NT1;
-        const int NTW = NT <= 2 ? 2 : NT <= 3 ? 3 : NT <= 4 ? 4 : NT <= 6 ? 6 : NT <= 8 ? 8 : 16;
-        const size_t rbytes = static_cast<size_t>(NTW) * root_kb;
-        const size_t wbytes = static_cast<size_t>(NTW) * frag_kb;
-        const size_t bbytes = static_cast<size_t>(NTW) * 16 * sizeof(float);
-        // W_l (fp32) shares the LDS when both fit; otherwise its fragments stream from L2
-        const bool has_l = wl_packed != nullptr && !narrow;
-        const bool wl_lds = has_l && rbytes + wbytes + bbytes <= lds_cap + 1024;
-        const size_t lds = rbytes + (wl_lds ? wbytes : 0) + bbytes;
-        const int64_t toff = (c0 / 16) * KG * 64;
-        RtArgs a;
-        a.x = x;
-        a.ldx = ldx;
-        a.K = static_cast<int>(K);
-        a.KG = KG;
-        a.n_rows = static_cast<int>(n_rows);
-        a.n_rows_dev = n_rows_dev;
-        a.rowptr = rowptr;
-        a.col = col;
-        // a slice's weights: packed fragments are n-tile major (contiguous
-        // sub-array); raw weights are rows [c0, c0 + Fo_c)
-        const int64_t woff = ldw ? c0 * ldw / 4 : toff;
-        a.wl = has_l ? static_cast<const v4f *>(wl_packed) + woff : nullptr;
-        a.wr = no_root ? nullptr : static_cast<const v4f *>(wr_packed) + woff;
-        a.wr_raw = (ldw && !no_root) ? static_cast<const float *>(wr_packed) + c0 * ldw : nullptr;
-        a.ldw = ldw;
-        a.C = C;
-        a.T4 = T4;
-        a.kpad = kpad;
-        // (the root image's launch packs the weights below when that image
-        // is prebuilt)
-        const bool img_pre = x3 && !no_root && img_ws && x3_image_bytes(NTW, C, T4, w1) <= kImgWsBytes;
-        a.wlp_src = nullptr;
-        a.wlp_dst = nullptr;
-        a.wlp_fo = 0;
-        if (ldw && has_l && !wl_lds) {
-            // raw W_l that must stream from L2: pack it once (all slices) into
-            // the caller's workspace -- fragment-ordered 1-KiB wave loads
-            // (one-part layers stream the bf16 image below instead: no fp32 pack)
-            if (c0 == 0 && !w1) {
-                if (!wl_ws || wl_ws_bytes < ngnn_pack_weight_bytes(Fo, K)) {
-                    *rc = NGNN_E_WORKSPACE;
-                    return 1;
-                }
-                // (NGNN_WL_PREPACKED: the producer packed this step's W_l there;
-                // with a prebuilt root image its launch packs it: one launch)
-                if (!wl_prepacked && img_pre) {
-                    a.wlp_src = static_cast<const float *>(wl_packed);
-                    a.wlp_dst = static_cast<v4f *>(wl_ws);
-                    a.wlp_fo = static_cast<int>(Fo);
-                }
-                const int prc = (wl_prepacked || img_pre) ? 0
-                                                          : ngnn_pack_weight(static_cast<const float *>(wl_packed),
-                                                                             ldw, Fo, K, wl_ws, st);
-                if (prc) {
-                    *rc = prc;
-                    return 1;
-                }
-            }
-            a.wl = static_cast<const v4f *>(wl_ws) + toff;
-        }
-        // one-part (bf16-exact) W_l streamed from L2: the neighbour term on
-        // bf16 MFMA from a bf16 image behind the packed fp32 one in the
-        // workspace (the kernel's W1 streamed form has no fp32 steps)
-        a.wlb = nullptr;
-        a.wlb_src = nullptr;
-        a.wlb_fo = static_cast<int>(Fo);
-        a.CL = static_cast<int>(ceil_div(K, 32));
-        if (w1 && has_l && !wl_lds) {
-            if (!ldw || !wl_ws || wl_ws_bytes < ngnn_pack_weight_bytes(Fo, K) + wl_b16_bytes(Fo, K)) {
-                *rc = NGNN_E_WORKSPACE;
-                return 1;
-            }
-            uint16_t *img16 = reinterpret_cast<uint16_t *>(static_cast<char *>(wl_ws) + ngnn_pack_weight_bytes(Fo, K));
-            if (c0 == 0 && img_pre) {
-                a.wlb = img16;
-                a.wlb_src = static_cast<const float *>(wl_packed);
-            } else if (c0 == 0) {
-                const int NTa = static_cast<int>(ceil_div(Fo, 16));
-                const int64_t total = static_cast<int64_t>(NTa) * a.CL * 512;
-                hipLaunchKernelGGL(k_pack_wl_b16, dim3(static_cast<unsigned>(ceil_div(total, 256))), dim3(256), 0, st,
-                                   static_cast<const float *>(wl_packed), ldw, static_cast<int>(Fo),
-                                   static_cast<int>(K), a.CL, NTa, img16);
-                *rc = launch_status();
-                if (*rc) return 1;
-            }
-            a.wlb = img16 + (c0 / 16) * a.CL * 64 * 8;
-        }
-        a.NT = NT;
-        a.NT1 = NT1;
-        // (unknown: every row may have in-edges -- no root-only phase)
-        a.n_edge = static_cast<int>(n_edge_rows < 0 ? n_rows : std::min(n_edge_rows, n_rows));
-        a.n_edge_dev = n_edge_rows_dev;
-        a.root_split = 0;
-        a.wz_raw = narrow ? static_cast<const float *>(wl_packed) : nullptr;
-        a.z = z;
-        a.ldz = ldz;
-        a.Fo = static_cast<int>(Fo_c);
-        a.out = out_bf16 ? reinterpret_cast<float *>(reinterpret_cast<uint16_t *>(out) + c0) : out + c0;
-        a.ldo = ldo;
-        a.vec_out = (Fo_c % 4 == 0) && (ldo % 4 == 0) && aligned(a.out, out_bf16 ? 8 : 16);
-        a.out_bf16 = out_bf16;
-        if (out_bf16 && !(a.vec_out && Fo_c % 16 == 0 && w1)) {  // bf16 rows: whole 16-column tiles of a one-part-image layer
+    if (NGNN_RT_FAST_BUILD && (!p.x3 || L.x_bf16 || p.w1 || L.reduce != NGNN_REDUCE_MEAN)) return 0;
+    const Dropout drop = make_dropout(L.p_drop, L.seed);
+    const bool has_l = L.wl != nullptr && !narrow;
+    const int n_tiles = static_cast<int>(ceil_div(L.n_rows, RT_ROWS));
+    for (int64_t c0 = 0; c0 < L.Fo; c0 += p.slice) {
+        const int64_t Fo_c = std::min<int64_t>(p.slice, L.Fo - c0);
+        const RtSlice s = rt_slice(p, Fo_c, has_l);
+        RtArgs a = slice_args(L, p, s, c0, Fo_c, has_l, drop);
+        // the split-bf16 root image built once (k_x3_image) into img_ws and
+        // DMA-copied by every workgroup (else each workgroup builds it)
+        const bool img_pre = p.x3 && !no_root && L.img_ws &&
+                             x3_image_bytes(s.NTW, p.im.C, p.im.T4, p.w1) <= kImgWsBytes;
+        if (has_l && !s.wl_lds && (*rc = stage_wl(L, p, c0, img_pre, a, st))) return 1;
+        if (L.out_bf16 && !(a.vec_out && Fo_c % 16 == 0 && p.w1)) {  // bf16 rows: whole 16-column tiles of a one-part-image layer
             *rc = NGNN_E_SHAPE;
             return 1;
         }
-        a.agg_out = (c0 == 0 && !narrow && !agg_pre) ? agg_out : nullptr;
-        a.ld_agg = ld_agg;
-        // later column slices read the aggregate the first one saved (the
-        // launches are stream-ordered) instead of gathering it again; agg_pre:
-        // every slice reads it (written by a separate aggregate launch)
-        a.agg_in = ((c0 > 0 || agg_pre) && !narrow && has_l) ? agg_out : nullptr;
-        a.epi = Epi{bias ? bias + c0 : nullptr, relu, drop, static_cast<int>(c0)};
-        a.seed_dev = seed_dev;
-        a.x_dev = x_dev;
-        a.xrow = xrow;
-        a.xrow_dev = xrow_dev;
-        a.x_rows = x_rows;
-        a.col_x = (xrow || xrow_dev) ? col_x : nullptr;
-        a.x_bf16 = x_bf16;
-        a.w1 = w1;
-        // the split-bf16 root image built once (k_x3_image) into img_ws and
-        // DMA-copied by every workgroup (else each workgroup builds it)
-        a.img = nullptr;
-        if (img_pre) {
-            *rc = build_image(a, NTW, img_ws, st);
-            if (*rc) return 1;
-        }
+        if (img_pre && (*rc = build_image(a, s.NTW, L.img_ws, st))) return 1;
         a.wlb_src = nullptr;
         a.wlp_src = nullptr;
-        const int n_tiles = static_cast<int>(ceil_div(n_rows, RT_ROWS));
-        // the tiles past the edge-row bound on k_root (ngnn_root.hip) when an
-        // instantiation covers this layer: k_sage_rt takes the tiles with
-        // in-edges (none in narrow mode), then k_root the rest
-        const bool vec = a.vec_out && (a.Fo == a.NT * 16);
-        const int form = (x3 && !NGNN_RT_STATIC && !no_root) ? rt_form(a, NTW, vec) : 0;
-        // policy (NGNN_ROOT, read once): 1 (default) k_root for layers with no
-        // in-kernel neighbour term (narrow mode: every tile); 2 also split the
-        // layers with edge tiles (k_sage_rt edge tiles, then k_root -- measured
-        // slower on products layer 0: the edge tiles alone then hold the GPU
-        // ~48 us, in one launch they overlap the root tiles); 0 never
-        static const int policy = [] {
-            const char *e = std::getenv("NGNN_ROOT");
-            return e ? std::atoi(e) : 1;
-        }();
-        const bool want_root = policy == 2 || (policy == 1 && !a.wl);
-        if (form && want_root && launch_root(a, NTW, form, vec, st, true) == NGNN_OK) {
-            if (a.wl) {
-                a.root_split = 1;
-                *rc = dispatch_rt(NTW, a, reduce, wl_lds, x3, n_tiles, lds, st);
-                if (*rc) return 1;
-                a.root_split = 0;
-            }
-            *rc = launch_root(a, NTW, form, vec, st);
-            if (*rc) return 1;
-            continue;
-        }
-        *rc = dispatch_rt(NTW, a, reduce, wl_lds, x3, n_tiles, lds, st);
-        if (*rc) return 1;
+        if ((*rc = launch_slice(a, p, s, L.reduce, n_tiles, st))) return 1;
     }
     return 1;
 }
@@ -777,17 +802,19 @@ extern "C" int ngnn_sage_fwd_raw(const float *x, const float *const *x_dev, cons
                                  int64_t ldo, int relu, float p_drop, uint64_t seed,
                                  const uint64_t *seed_dev, float *agg_out, int64_t ld_agg, void *ws,
                                  size_t ws_bytes, void *stream) {
-    const bool exact = (reduce & NGNN_MATH_EXACT_F32) != 0;
+    // the flag bits of `reduce`, decoded once into the call descriptor
+    LayerFwd L;
+    L.exact = (reduce & NGNN_MATH_EXACT_F32) != 0;
     const bool want_narrow = (reduce & NGNN_FWD_NARROW) != 0;
-    const bool x_bf16 = (reduce & NGNN_X_BF16) != 0;
-    const bool w_bf16 = (reduce & NGNN_W_BF16) != 0;
-    const bool wl_prepacked = (reduce & NGNN_WL_PREPACKED) != 0;
-    const bool out_bf16 = (reduce & NGNN_OUT_BF16) != 0;
+    L.x_bf16 = (reduce & NGNN_X_BF16) != 0;
+    L.w_bf16 = (reduce & NGNN_W_BF16) != 0;
+    L.wl_prepacked = (reduce & NGNN_WL_PREPACKED) != 0;
+    L.out_bf16 = (reduce & NGNN_OUT_BF16) != 0;
     reduce &= ~(NGNN_MATH_EXACT_F32 | NGNN_FWD_NARROW | NGNN_X_BF16 | NGNN_W_BF16 |
                 NGNN_WL_PREPACKED | NGNN_OUT_BF16);
     // bf16 rows: the split-bf16 root term only
-    if (x_bf16 && exact) return NGNN_E_SHAPE;
-    if (out_bf16 && want_narrow) return NGNN_E_SHAPE;
+    if (L.x_bf16 && L.exact) return NGNN_E_SHAPE;
+    if (L.out_bf16 && want_narrow) return NGNN_E_SHAPE;
     NGNN_RETURN_IF(reduce < NGNN_REDUCE_SUM || reduce > NGNN_REDUCE_MAX, NGNN_E_ARG);
     // wr == NULL: no root term (GCNConv = SAGEConv with W_r = 0: the layer
     // aggregates first, out = act(b + agg(x) W_l^T))
@@ -801,6 +828,13 @@ extern "C" int ngnn_sage_fwd_raw(const float *x, const float *const *x_dev, cons
     if (n_rows == 0) return NGNN_OK;
     NGNN_RETURN_IF((!x && !x_dev) || !out, NGNN_E_ARG);
     hipStream_t st = as_stream(stream);
+    L.x = x, L.x_dev = x_dev, L.xrow = xrow, L.xrow_dev = xrow_dev, L.x_rows = x_rows, L.col_x = col_x, L.ldx = ldx;
+    L.K = K, L.Fo = Fo, L.n_rows = n_rows, L.n_rows_dev = n_rows_dev;
+    L.n_edge_rows = n_edge_rows, L.n_edge_rows_dev = n_edge_rows_dev;
+    L.rowptr = rowptr, L.col = col, L.reduce = reduce;
+    L.wl = wl, L.wr = wr, L.ldw = ldw, L.bias = bias;
+    L.out = out, L.ldo = ldo, L.relu = relu, L.p_drop = p_drop, L.seed = seed, L.seed_dev = seed_dev;
+    L.agg_out = agg_out, L.ld_agg = ld_agg, L.ws = ws, L.ws_bytes = ws_bytes;
     int rc = NGNN_OK;
     // narrow mode (MEAN / SUM): the neighbour term aggregated in the F_out-wide
     // space (z = x W_l^T, then a gather of z), no saved aggregate
@@ -809,7 +843,6 @@ extern "C" int ngnn_sage_fwd_raw(const float *x, const float *const *x_dev, cons
     // when the rest still holds z (narrow) / a packed W_l
     const size_t head = want_narrow ? static_cast<size_t>(n_rows) * ldz * sizeof(float)
                                     : ngnn_pack_weight_bytes(Fo, K) + wl_b16_bytes(Fo, K);
-    void *img_ws = nullptr;
     // (NGNN_IMG=0, read once: every workgroup builds its image -- A/B only)
     static const bool img_on = [] {
         const char *e = std::getenv("NGNN_IMG");
@@ -817,18 +850,18 @@ extern "C" int ngnn_sage_fwd_raw(const float *x, const float *const *x_dev, cons
     }();
     if (img_on && ws && aligned(ws, 16) && ws_bytes >= head + kImgWsBytes + 16) {
         const uintptr_t e = (reinterpret_cast<uintptr_t>(ws) + ws_bytes - kImgWsBytes) & ~uintptr_t(15);
-        img_ws = reinterpret_cast<void *>(e);
+        L.img_ws = reinterpret_cast<void *>(e);
     }
     if (want_narrow && wl && reduce != NGNN_REDUCE_MAX && !agg_out && !relu && !(p_drop > 0.0f) &&
         ws && aligned(ws, 16) &&
         ws_bytes >= static_cast<size_t>(n_rows) * ldz * sizeof(float)) {
-        float *z = static_cast<float *>(ws);
-        if (sage_fwd_rowtile(x, ldx, K, n_rows, n_rows_dev, rowptr, col, reduce, wl, wr, bias, Fo,
-                             out, ldo, relu, p_drop, seed, seed_dev, nullptr, K, st, &rc, ldw,
-                             nullptr, 0, x_dev, exact, z, ldz, xrow, xrow_dev, x_rows, col_x, x_bf16,
-                             w_bf16, false, false, false, n_edge_rows, n_edge_rows_dev, img_ws)) {
+        LayerFwd n = L;  // (the workspace holds z; no saved aggregate)
+        n.z = static_cast<float *>(ws);
+        n.ldz = ldz;
+        n.agg_out = nullptr;
+        if (sage_fwd_rowtile(n, st, &rc)) {
             if (rc) return rc;
-            return narrow_agg_launch(z, ldz, Fo, rowptr, col, n_rows, n_rows_dev, n_edge_rows,
+            return narrow_agg_launch(n.z, ldz, Fo, rowptr, col, n_rows, n_rows_dev, n_edge_rows,
                                      n_edge_rows_dev, reduce, out, ldo, st, nullptr);
         }
     }
@@ -836,11 +869,9 @@ extern "C" int ngnn_sage_fwd_raw(const float *x, const float *const *x_dev, cons
     // or K % 4 != 0): aggregate launch + 2-D tiled dual GEMM
     // (x_dev: a graph slot's batch rows in place -- K % 4 != 0 rows too, the
     // wide kernels load them at 4-B alignment)
-    if ((x || x_dev) && !xrow && !xrow_dev && !x_bf16 && !out_bf16 && sage_wide_preferred(K, Fo, exact) &&
+    if ((x || x_dev) && !xrow && !xrow_dev && !L.x_bf16 && !L.out_bf16 && sage_wide_preferred(K, Fo, L.exact) &&
         (agg_out || !wl || ws_bytes >= sage_wide_workspace_bytes(K, n_edge_rows)))
-        return sage_fwd_wide(x, ldx, K, n_rows, n_rows_dev, n_edge_rows, n_edge_rows_dev, rowptr,
-                             col, reduce, wl, wr, ldw, bias, Fo, out, ldo, relu, p_drop, seed,
-                             seed_dev, agg_out, ld_agg, ws, ws_bytes, st, exact, x_dev);
+        return sage_fwd_wide(L, st);
     // max layers with a wide input: the aggregate by its own launch (a wave per
     // row, every column in flight) into the saved-aggregate buffer, which the
     // row-tile kernel's edge tiles then read densely -- its in-kernel gather
@@ -853,20 +884,14 @@ extern "C" int ngnn_sage_fwd_raw(const float *x, const float *const *x_dev, cons
         const char *e = std::getenv("NGNN_AGGPRE");
         return e ? std::atoi(e) : 0;
     }();
-    const bool agg_pre = (reduce == NGNN_REDUCE_MAX ? K >= 256 : aggpre_all == 1) && wl && agg_out &&
-                         (x || x_dev) && !xrow && !xrow_dev && !x_bf16 && ld_agg % 4 == 0 &&
-                         aligned(agg_out, 16);
-    if (agg_pre) {
-        rc = sage_wide_aggregate(x, ldx, K, n_rows, n_rows_dev, n_edge_rows, n_edge_rows_dev, rowptr,
-                                 col, reduce, agg_out, ld_agg, st, x_dev);
+    L.agg_pre = (reduce == NGNN_REDUCE_MAX ? K >= 256 : aggpre_all == 1) && wl && agg_out &&
+                (x || x_dev) && !xrow && !xrow_dev && !L.x_bf16 && ld_agg % 4 == 0 &&
+                aligned(agg_out, 16);
+    if (L.agg_pre) {
+        rc = sage_wide_aggregate(L, st);
         if (rc) return rc;
     }
-    if (!sage_fwd_rowtile(x, ldx, K, n_rows, n_rows_dev, rowptr, col, reduce, wl, wr, bias, Fo, out,
-                          ldo, relu, p_drop, seed, seed_dev, agg_out, ld_agg, st, &rc, ldw, ws,
-                          ws_bytes, x_dev, exact, nullptr, 0, xrow, xrow_dev, x_rows, col_x, x_bf16,
-                          w_bf16, wl_prepacked, agg_pre, out_bf16, n_edge_rows, n_edge_rows_dev,
-                          img_ws))
-        return NGNN_E_SHAPE;  // outside the row-tile envelope: pack + ngnn_sage_fwd
+    if (!sage_fwd_rowtile(L, st, &rc)) return NGNN_E_SHAPE;  // outside the row-tile envelope: pack + ngnn_sage_fwd
     return rc;
 }
 

@@ -832,22 +832,13 @@ size_t wide_wimg_bytes(int64_t K, int64_t Fo) {
 // it within two slices, fused.pad_k_ok).  Its f32 MFMA rate is 1/2.7 of the
 // row-tile kernel's split-bf16 root term, so moderately sliced layers (the
 // 256 -> 256 hidden layer: 3 slices) stay on the row-tile kernel.
+// The slice width is rt_root_image's (ngnn_sage_rt.hip, the single envelope
+// function) for raw fp32 weights with a root term -- the LayerFwd calls this
+// query routes -- at the full tile ladder: the A/B build flag NGNN_RT_MAXNTW
+// narrows sage_fwd_rowtile's slices only, not this routing.
 bool sage_wide_preferred(int64_t K, int64_t Fo, bool exact) {
     if (K % 4 != 0) return true;
-    const int64_t KG = ceil_div(K, 16);
-    int64_t C = K / 32, T4 = ceil_div(K % 32, 4);
-    if (T4 > 3) {  // X3_TAIL_MAX (ngnn_sage_rt.hip): the tail becomes a padded chunk
-        C += 1;
-        T4 = 0;
-    }
-    const int64_t img = exact ? KG * 64 * 16 : 3 * C * 64 * 16 + T4 * 64 * 4;
-    const int64_t cap = 160 * 1024 - 1024 - 256;
-    int ntw = 0;
-    for (int c : {16, 8, 6, 4, 3, 2})
-        if (c * img <= cap) {
-            ntw = c;
-            break;
-        }
+    const int ntw = rt_root_image(K, !exact, false, false, 16).ntw_max;
     return ntw == 0 || ceil_div(Fo, 16 * ntw) > 4;
 }
 
@@ -855,14 +846,45 @@ size_t sage_wide_workspace_bytes(int64_t K, int64_t n_rows) {
     return static_cast<size_t>(std::max<int64_t>(n_rows, 0)) * static_cast<size_t>(K) * sizeof(float);
 }
 
-int sage_fwd_wide(const float *x, int64_t ldx, int64_t K, int64_t n_rows,
-                  const int32_t *n_rows_dev, int64_t n_edge_rows, const int32_t *n_edge_rows_dev,
-                  const int32_t *rowptr, const int32_t *col, int reduce, const float *wl,
-                  const float *wr, int64_t ldw, const float *bias, int64_t Fo, float *out,
-                  int64_t ldo, int relu, float p_drop, uint64_t seed, const uint64_t *seed_dev,
-                  float *agg_out, int64_t ld_agg, void *ws, size_t ws_bytes, hipStream_t st, bool exact,
-                  const float *const *x_dev) {
-    const int64_t n_edge = std::max<int64_t>(0, std::min(n_edge_rows, n_rows));
+namespace {
+
+// the aggregate's workgroups: a wave per row, 4 rows each
+unsigned wide_agg_blocks(int64_t n_edge) {
+    return static_cast<unsigned>(std::min<int64_t>(ceil_div(n_edge, 4), 8 * num_cus()));
+}
+
+// k_wide_agg of rows [0, n_edge) of L into agg (row stride lda) on `grid`
+// workgroups, instantiated by reduce and by the columns a lane holds per pass
+// (4 / 8 / 12 of 64).  prep, ea: the H2 layer's preparation riding on this
+// launch (workgroups past prep.n_agg) and the rows' staging exponents, or
+// empty / null.
+int launch_wide_agg(const LayerFwd &L, int64_t n_edge, unsigned grid, float *agg, int64_t lda, int round16, int *ea,
+                    const WidePrep &prep, hipStream_t st) {
+    auto launch_agg = [&](auto red_c, auto nc_c) {
+        hipLaunchKernelGGL((k_wide_agg<decltype(red_c)::value, decltype(nc_c)::value>), dim3(grid), dim3(256), 0, st,
+                           L.x, L.ldx, static_cast<int>(L.K), L.rowptr, L.col, static_cast<int>(n_edge),
+                           L.n_rows_dev, L.n_edge_rows_dev, agg, lda, static_cast<int>(L.n_rows), round16, L.x_dev,
+                           ea, prep);
+    };
+    auto by_nc = [&](auto red_c) {
+        if (L.K <= 256) launch_agg(red_c, std::integral_constant<int, 4>{});
+        else if (L.K <= 512) launch_agg(red_c, std::integral_constant<int, 8>{});
+        else launch_agg(red_c, std::integral_constant<int, 12>{});  // (> 768: passes of 768)
+    };
+    if (L.reduce == NGNN_REDUCE_MEAN) by_nc(std::integral_constant<int, NGNN_REDUCE_MEAN>{});
+    else if (L.reduce == NGNN_REDUCE_SUM) by_nc(std::integral_constant<int, NGNN_REDUCE_SUM>{});
+    else by_nc(std::integral_constant<int, NGNN_REDUCE_MAX>{});
+    return launch_status();
+}
+
+}  // namespace
+
+int sage_fwd_wide(const LayerFwd &L, hipStream_t st) {
+    const int64_t K = L.K, Fo = L.Fo, n_rows = L.n_rows;
+    const float *const wl = static_cast<const float *>(L.wl), *const wr = static_cast<const float *>(L.wr);
+    void *const ws = L.ws;
+    const size_t ws_bytes = L.ws_bytes;
+    const int64_t n_edge = std::max<int64_t>(0, std::min(L.n_edge_rows, n_rows));
     // the H2 form (NGNN_WIDE_H2=0, read once: X3 -- A/B): an even number of
     // k-stages (its root / neighbour loops each start on buffer 0), 32-bit row
     // offsets, and room for the 2-part image + the row / column exponents at
@@ -873,13 +895,13 @@ int sage_fwd_wide(const float *x, int64_t ldx, int64_t K, int64_t n_rows,
         return !(e && e[0] == '0');
     }();
     const bool has_agg = wl && n_edge > 0;
-    const int64_t lda_eff = agg_out ? ld_agg : K;
-    const bool fits = n_rows * ldx * 4 < 0x7FFF0000ll && (!has_agg || n_edge * lda_eff * 4 < 0x7FFF0000ll);
-    const size_t head = has_agg && (!agg_out || agg_out == ws) ? sage_wide_workspace_bytes(K, n_edge) : 0;
+    const int64_t lda_eff = L.agg_out ? L.ld_agg : K;
+    const bool fits = n_rows * L.ldx * 4 < 0x7FFF0000ll && (!has_agg || n_edge * lda_eff * 4 < 0x7FFF0000ll);
+    const size_t head = has_agg && (!L.agg_out || L.agg_out == ws) ? sage_wide_workspace_bytes(K, n_edge) : 0;
     const int Kp = static_cast<int>(ceil_div(K, 32) * 32);
     const size_t ib2 = static_cast<size_t>(4) * Fo * Kp * 2;
     const size_t side = (static_cast<size_t>(2) * Fo + n_rows + n_edge) * 4 + 1024;
-    const bool use_h2 = !exact && h2_on && fits && ceil_div(K, WKC) % 2 == 0 && ws && ws_bytes >= head + ib2 + side + 512;
+    const bool use_h2 = !L.exact && h2_on && fits && ceil_div(K, WKC) % 2 == 0 && ws && ws_bytes >= head + ib2 + side + 512;
     _Float16 *h2_img = nullptr;
     int *ew = nullptr, *ex = nullptr, *ea = nullptr;
     if (use_h2) {
@@ -889,68 +911,53 @@ int sage_fwd_wide(const float *x, int64_t ldx, int64_t K, int64_t n_rows,
         ex = ew + 2 * Fo;
         ea = ex + n_rows;
     }
-    int *const agg_ea = ea;
     // the preparation's workgroups: 4 W rows each, then one wave per x row
     // (capped); riding on the aggregate's launch when there is one
     WidePrep prep{};
     unsigned prep_blocks = 0;
     if (use_h2) {
-        prep = WidePrep{wr, wl, ldw, static_cast<int>(Fo), Kp, h2_img, ew, static_cast<int>(ceil_div(2 * Fo, 4)),
+        prep = WidePrep{wr, wl, L.ldw, static_cast<int>(Fo), Kp, h2_img, ew, static_cast<int>(ceil_div(2 * Fo, 4)),
                         static_cast<int>(n_rows), ex, 0};
         const int64_t gr = std::max<int64_t>(1, std::min<int64_t>(ceil_div(n_rows, 4), 8 * num_cus()));
         prep_blocks = static_cast<unsigned>(prep.nbw + gr);
     }
     bool prep_done = false;
     float *agg = nullptr;
-    int64_t lda = ld_agg;
+    int64_t lda = L.ld_agg;
     if (has_agg) {
-        if (agg_out) {
-            agg = agg_out;
+        if (L.agg_out) {
+            agg = L.agg_out;
         } else {
             NGNN_RETURN_IF(!ws || ws_bytes < sage_wide_workspace_bytes(K, n_edge) || !aligned(ws, 4),
                            NGNN_E_WORKSPACE);
             agg = static_cast<float *>(ws);
             lda = K;
         }
-        const unsigned ga = static_cast<unsigned>(std::min<int64_t>(ceil_div(n_edge, 4), 8 * num_cus()));
+        const unsigned ga = wide_agg_blocks(n_edge);
         prep.n_agg = static_cast<int>(ga);
         prep_done = use_h2;
-        auto launch_agg = [&](auto red_c, auto nc_c) {
-            hipLaunchKernelGGL((k_wide_agg<decltype(red_c)::value, decltype(nc_c)::value>), dim3(ga + prep_blocks),
-                               dim3(256), 0, st, x, ldx, static_cast<int>(K), rowptr, col,
-                               static_cast<int>(n_edge), n_rows_dev, n_edge_rows_dev, agg, lda,
-                               static_cast<int>(n_rows), 0, x_dev, agg_ea, prep);
-        };
-        auto by_nc = [&](auto red_c) {
-            if (K <= 256) launch_agg(red_c, std::integral_constant<int, 4>{});
-            else if (K <= 512) launch_agg(red_c, std::integral_constant<int, 8>{});
-            else launch_agg(red_c, std::integral_constant<int, 12>{});  // (> 768: passes of 768)
-        };
-        if (reduce == NGNN_REDUCE_MEAN) by_nc(std::integral_constant<int, NGNN_REDUCE_MEAN>{});
-        else if (reduce == NGNN_REDUCE_SUM) by_nc(std::integral_constant<int, NGNN_REDUCE_SUM>{});
-        else by_nc(std::integral_constant<int, NGNN_REDUCE_MAX>{});
-        const int rc = launch_status();
+        const int rc = launch_wide_agg(L, n_edge, ga + prep_blocks, agg, lda, 0, ea, prep, st);
         if (rc) return rc;
     }
-    WideArgs a;
-    a.x = x;
-    a.x_dev = x_dev;
-    a.ldx = ldx;
+    WideArgs a{};
+    a.x = L.x;
+    a.x_dev = L.x_dev;
+    a.ldx = L.ldx;
     a.agg = agg;
     a.ld_agg = lda;
     a.wr = wr;
     a.wl = wl;
-    a.ldw = ldw;
+    a.ldw = L.ldw;
     a.K = static_cast<int>(K);
     a.Fo = static_cast<int>(Fo);
     a.n_rows = static_cast<int>(n_rows);
     a.n_edge = static_cast<int>(n_edge);
-    a.n_rows_dev = n_rows_dev;
-    a.n_edge_dev = n_edge_rows_dev;
-    a.out = out;
-    a.ldo = ldo;
-    a.epi = Epi{bias, relu, make_dropout(p_drop, seed), 0};
-    a.seed_dev = seed_dev;
+    a.n_rows_dev = L.n_rows_dev;
+    a.n_edge_dev = L.n_edge_rows_dev;
+    a.out = L.out;
+    a.ldo = L.ldo;
+    a.epi = Epi{L.bias, L.relu, make_dropout(L.p_drop, L.seed), 0};
+    a.seed_dev = L.seed_dev;
     a.n_ct = static_cast<int>(ceil_div(Fo, WBN));
     // (NGNN_WIDE_XCD=0, read once: k_wide_h2's plain tile order -- A/B)
     static const bool xcd_on = [] {
@@ -963,7 +970,7 @@ int sage_fwd_wide(const float *x, int64_t ldx, int64_t K, int64_t n_rows,
     // persistent: two workgroups per CU (55 KiB LDS, 178 VGPRs each), a
     // multiple of 8 (one per XCD in turn)
     const int64_t grid = std::max<int64_t>(8, std::min<int64_t>(ceil_div(tiles, 8) * 8, 2 * num_cus()));
-    const bool vout = (ldo % 4 == 0) && aligned(out, 16);
+    const bool vout = (L.ldo % 4 == 0) && aligned(L.out, 16);
     // the split-bf16 form (not under NGNN_MATH_EXACT_F32): its weight image at
     // the workspace's tail (NGNN_WIDE_X3=0, read once: the exact f32 form -- A/B)
     static const bool x3_on = [] {
@@ -975,8 +982,8 @@ int sage_fwd_wide(const float *x, int64_t ldx, int64_t K, int64_t n_rows,
         if (use_h2) {
             _Float16 *img = h2_img;
             if (!prep_done) {
-                hipLaunchKernelGGL(k_wide_prep_h2, dim3(prep_blocks), dim3(256), 0, st, prep, x, x_dev, ldx,
-                                   static_cast<int>(K), n_rows_dev);
+                hipLaunchKernelGGL(k_wide_prep_h2, dim3(prep_blocks), dim3(256), 0, st, prep, L.x, L.x_dev, L.ldx,
+                                   static_cast<int>(K), L.n_rows_dev);
                 const int rc = launch_status();
                 if (rc) return rc;
             }
@@ -1006,12 +1013,12 @@ int sage_fwd_wide(const float *x, int64_t ldx, int64_t K, int64_t n_rows,
             return vout ? go(k_wide_h2<true, 64>, 64) : go(k_wide_h2<false, 64>, 64);
         }
     }
-    if (!exact && x3_on && fits && ws && ws_bytes >= head + ib + 256) {
+    if (!L.exact && x3_on && fits && ws && ws_bytes >= head + ib + 256) {
         const uintptr_t e = (reinterpret_cast<uintptr_t>(ws) + ws_bytes - ib) & ~uintptr_t(255);
         __bf16 *img = reinterpret_cast<__bf16 *>(e);
         const int64_t nthr = static_cast<int64_t>(2) * Fo * Kp / 8;
         hipLaunchKernelGGL(k_wide_wimg, dim3(static_cast<unsigned>(ceil_div(nthr, 256))), dim3(256), 0, st, wr, wl,
-                           ldw, static_cast<int>(Fo), static_cast<int>(K), Kp, img);
+                           L.ldw, static_cast<int>(Fo), static_cast<int>(K), Kp, img);
         int rc = launch_status();
         if (rc) return rc;
         const size_t lds = static_cast<size_t>(2) * XW_STAGE * 2;
@@ -1036,35 +1043,14 @@ int sage_fwd_wide(const float *x, int64_t ldx, int64_t K, int64_t n_rows,
     return launch_status();
 }
 
-}  // namespace ngnn
-
-namespace ngnn {
 // The aggregate of rows [0, ceil16(min(n_edge_rows, *n_edge_rows_dev))) into
-// agg (ld_agg), for the row-tile kernel's pre-aggregated max layers.
-int sage_wide_aggregate(const float *x, int64_t ldx, int64_t K, int64_t n_rows,
-                        const int32_t *n_rows_dev, int64_t n_edge_rows,
-                        const int32_t *n_edge_rows_dev, const int32_t *rowptr, const int32_t *col,
-                        int reduce, float *agg, int64_t ld_agg, hipStream_t st,
-                        const float *const *x_dev) {
-    const int64_t n_edge = std::max<int64_t>(0, std::min(ceil_div(n_edge_rows, 16) * 16, n_rows));
+// L.agg_out (ld_agg), for the row-tile kernel's pre-aggregated max layers.
+int sage_wide_aggregate(const LayerFwd &L, hipStream_t st) {
+    const int64_t n_edge = std::max<int64_t>(0, std::min(ceil_div(L.n_edge_rows, 16) * 16, L.n_rows));
     if (n_edge == 0) return NGNN_OK;
-    const unsigned ga = static_cast<unsigned>(std::min<int64_t>(ceil_div(n_edge, 4), 8 * num_cus()));
-    auto launch_agg = [&](auto red_c, auto nc_c) {
-        hipLaunchKernelGGL((k_wide_agg<decltype(red_c)::value, decltype(nc_c)::value>), dim3(ga),
-                           dim3(256), 0, st, x, ldx, static_cast<int>(K), rowptr, col,
-                           static_cast<int>(n_edge), n_rows_dev, n_edge_rows_dev, agg, ld_agg,
-                           static_cast<int>(n_rows), 1, x_dev, nullptr, WidePrep{});
-    };
-    auto by_nc = [&](auto red_c) {
-        if (K <= 256) launch_agg(red_c, std::integral_constant<int, 4>{});
-        else if (K <= 512) launch_agg(red_c, std::integral_constant<int, 8>{});
-        else launch_agg(red_c, std::integral_constant<int, 12>{});
-    };
-    if (reduce == NGNN_REDUCE_MEAN) by_nc(std::integral_constant<int, NGNN_REDUCE_MEAN>{});
-    else if (reduce == NGNN_REDUCE_SUM) by_nc(std::integral_constant<int, NGNN_REDUCE_SUM>{});
-    else by_nc(std::integral_constant<int, NGNN_REDUCE_MAX>{});
-    return launch_status();
+    return launch_wide_agg(L, n_edge, wide_agg_blocks(n_edge), L.agg_out, L.ld_agg, 1, nullptr, WidePrep{}, st);
 }
+
 }  // namespace ngnn
 
 extern "C" int ngnn_sage_wide_preferred(int64_t K, int64_t Fo, int exact) {

@@ -161,6 +161,30 @@ def _gemm_layer(x, K, n_rows, block, reduce, pl, pr, bias, Fo, out, relu, p_drop
     _lib.check(rc, "ngnn_sage_fwd")
 
 
+def _fwd_raw(x, *, x_dev=None, xrow=None, xrow_dev=None, x_rows=0, n_rows=None, n_rows_dev=None,
+             n_edge_rows=None, n_edge_rows_dev=None, rowptr=None, col=None, col_x=None,
+             reduce="sum", flags=0, wl=None, wr=None, bias=None, out=None, relu=False, p_drop=0.0,
+             seed=0, seed_dev=None, agg_out=None, ws=None) -> int:
+    """The package's one ngnn_sage_fwd_raw call (include/ngnn.h): tensors by
+    keyword, None = absent.  K, F_out, the row strides, the workspace's bytes
+    and the stream come from the tensors; n_rows defaults to x's rows and
+    n_edge_rows to n_rows; the exact-fp32 mode joins `flags`.  Returns the
+    raw status (E_SHAPE is the caller's to handle)."""
+    w = wl if wl is not None else wr
+    K = x.size(1)
+    n_rows = x.size(0) if n_rows is None else n_rows
+    return _lib.load().ngnn_sage_fwd_raw(
+        _lib.ptr(x), _lib.ptr(x_dev), _lib.ptr(xrow), _lib.ptr(xrow_dev), int(x_rows), x.stride(0),
+        K, n_rows, _lib.ptr(n_rows_dev), n_rows if n_edge_rows is None else n_edge_rows,
+        _lib.ptr(n_edge_rows_dev), _lib.ptr(rowptr), _lib.ptr(col), _lib.ptr(col_x),
+        _lib.REDUCE[reduce] | flags | (_lib.MATH_EXACT_F32 if _exact_f32 else 0),
+        _lib.ptr(wl), _lib.ptr(wr), w.stride(0), _lib.ptr(bias), w.shape[0],
+        _lib.ptr(out), out.stride(0), int(relu), float(p_drop), seed & (2**64 - 1), _lib.ptr(seed_dev),
+        _lib.ptr(agg_out), agg_out.stride(0) if agg_out is not None else K,
+        _lib.ptr(ws), ws.numel() * ws.element_size() if ws is not None else 0,
+        _lib.stream_handle(x.device))
+
+
 def narrow_ok(reduce: str, K: int, Fo: int, relu: bool, p_drop: float) -> bool:
     """Can this layer aggregate its neighbour term in the F_out-wide space
     (NGNN_FWD_NARROW)?  A linear aggregation into a narrower output layer
@@ -239,7 +263,6 @@ def sage_layer_fwd(x: torch.Tensor, block: Block, reduce: str, wl, bl, wr, relu:
         xk[:, :K].copy_(x)
         wl_ = _pad_cols(wl_, K4)
         wr_ = _pad_cols(wr_, K4) if root else None
-    nrd = _lib.ptr(block.n_rows_dev) if block.n_rows_dev is not None else None
     lib = _lib.load()
     if (not xb and xrow_dev is None and not (narrow and agg_out is None)
             and lib.ngnn_sage_wide_preferred(xk.size(1), Fo, int(_exact_f32))):
@@ -256,29 +279,26 @@ def sage_layer_fwd(x: torch.Tensor, block: Block, reduce: str, wl, bl, wr, relu:
         # raw weights straight into the row-tile kernel; packed fallback otherwise
         # rows >= n_active have no in-edges (a sampler-built block): dense kernel
         n_edge = N if block.n_active is None else min(int(block.n_active), N)
-        rc = lib.ngnn_sage_fwd_raw(
-            _lib.ptr(xk), _lib.ptr(x_dev), None, _lib.ptr(xrow_dev), int(x_rows), xk.stride(0),
-            xk.size(1), N, nrd, n_edge,
-            _lib.ptr(block.n_edge_rows_dev), _lib.ptr(block.rowptr), _lib.ptr(block.col),
-            _lib.ptr(block.col_x) if xrow_dev is not None else None,
-            _lib.REDUCE[reduce] | (_lib.MATH_EXACT_F32 if _exact_f32 else 0)
-            | (_lib.FWD_NARROW if (narrow and agg_out is None) else 0)
-            | (_lib.X_BF16 if xb else 0) | (_lib.W_BF16 if w1 else 0) | prepacked
-            | (_lib.OUT_BF16 if out_bf16 else 0),
-            _lib.ptr(wl_), _lib.ptr(wr_), wl_.stride(0), _lib.ptr(bl), Fo,
-            _lib.ptr(out), out.stride(0), int(relu), float(p_drop), seed & (2**64 - 1),
-            _lib.ptr(seed_dev), _lib.ptr(agg_out),
-            agg_out.stride(0) if agg_out is not None else xk.size(1),
-            _lib.ptr(ws), ws.numel() * ws.element_size(), _lib.stream_handle(x.device))
+        flags = ((_lib.FWD_NARROW if (narrow and agg_out is None) else 0)
+                 | (_lib.X_BF16 if xb else 0) | (_lib.W_BF16 if w1 else 0) | prepacked
+                 | (_lib.OUT_BF16 if out_bf16 else 0))
+        rc = _fwd_raw(xk, x_dev=x_dev, xrow_dev=xrow_dev, x_rows=x_rows, n_rows=N,
+                      n_rows_dev=block.n_rows_dev, n_edge_rows=n_edge,
+                      n_edge_rows_dev=block.n_edge_rows_dev, rowptr=block.rowptr, col=block.col,
+                      col_x=block.col_x if xrow_dev is not None else None, reduce=reduce, flags=flags,
+                      wl=wl_, wr=wr_, bias=bl, out=out, relu=relu, p_drop=p_drop, seed=seed,
+                      seed_dev=seed_dev, agg_out=agg_out, ws=ws)
         if rc == _lib.E_SHAPE and out_bf16:
             # this layer's kernel writes fp32 rows only
-            return sage_layer_fwd(x, block, reduce, wl, bl, wr, relu, p_drop, seed, agg_out,
-                                  seed_dev, x_dev, span, narrow, xrow_dev, x_rows, w_bf16,
-                                  wl_packed, out_bf16=False)
+            return sage_layer_fwd(x, block, reduce, wl, bl, wr, relu, p_drop, seed, agg_out=agg_out,
+                                  seed_dev=seed_dev, x_dev=x_dev, span=span, narrow=narrow,
+                                  xrow_dev=xrow_dev, x_rows=x_rows, w_bf16=w_bf16,
+                                  wl_packed=wl_packed, out_bf16=False)
         if rc == _lib.E_SHAPE and xb and x_dev is None:
             # bf16 rows outside the bf16 envelope: the fp32 path on widened rows
             return sage_layer_fwd(x.float(), block, reduce, wl, bl, wr, relu, p_drop, seed,
-                                  agg_out, seed_dev, None, span, narrow, w_bf16=w_bf16)
+                                  agg_out=agg_out, seed_dev=seed_dev, span=span, narrow=narrow,
+                                  w_bf16=w_bf16)
         if rc == _lib.E_SHAPE:
             if x_dev is not None:
                 raise _lib.NGNNError("zero-copy input outside the row-tile kernel's envelope")
@@ -309,7 +329,11 @@ def pad_k_ok(K: int, Fo: int = 0) -> bool:
     16 outputs) must fit the LDS for enough output tiles that F_out takes at
     most two column slices (each slice re-reads x: measured on
     Amazon-Computers' 767 -> 512 layer, 16 slices ran 1.4x slower than the
-    64-row kernel)."""
+    64-row kernel).  Mirrors rt_root_image (csrc/ngnn_sage_rt.hip, the C++
+    envelope: same LDS cap and tile-count ladder) for a split-bf16 image,
+    with a K4 % 32 tail counted as a whole chunk (the C++ image of a tail of
+    <= 12 columns is smaller, never larger); tests/test_loader_cpu.py
+    restates the rule."""
     K4 = K + (-K) % 4
     img = 3 * (-(-K4 // 32)) * 1024
     ntw = next((c for c in (16, 8, 6, 4, 3, 2) if c * img <= 160 * 1024 - 1280), 0)
@@ -363,12 +387,8 @@ def gcn_transform_first(x, block: Block, w, b, relu: bool, p_drop: float, seed: 
     out = torch.empty(N, Fo, dtype=torch.float32, device=x.device)
     root_rate = MFMA_F32_TFS * 1e12 * (1.0 if _exact_f32 else 16.0 / 6.0)
     with _timing.span(span + "_z", (N * K + N * ldz) * 4, 2 * N * K * Fo, 2 * N * K * Fo / root_rate):
-        rc = lib.ngnn_sage_fwd_raw(
-            _lib.ptr(x), _lib.ptr(x_dev), None, _lib.ptr(xrow_dev), int(x_rows), x.stride(0), K, N,
-            nrd, N, None, _lib.ptr(block.rowptr),
-            _lib.ptr(block.col), None, _lib.REDUCE["sum"] | (_lib.MATH_EXACT_F32 if _exact_f32 else 0),
-            None, _lib.ptr(wd), wd.stride(0), None, Fo, _lib.ptr(z), ldz, 0, 0.0, 0, None, None, K,
-            _lib.ptr(ws), ws.numel(), _lib.stream_handle(x.device))
+        rc = _fwd_raw(x, x_dev=x_dev, xrow_dev=xrow_dev, x_rows=x_rows, n_rows_dev=block.n_rows_dev,
+                      rowptr=block.rowptr, col=block.col, reduce="sum", wr=wd, out=z, ws=ws)
         if rc == _lib.E_SHAPE:
             if x_dev is not None:
                 raise _lib.NGNNError("zero-copy input outside the row-tile kernel's envelope")

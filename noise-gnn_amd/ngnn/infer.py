@@ -119,10 +119,6 @@ def _chunks(N: int, bs: int, width: int, fanout: int):
     return [(r0, min(r0 + step, N)) for r0 in range(0, N, step)]
 
 
-def _flags(reduce: str) -> int:
-    return _lib.REDUCE[reduce] | (_lib.MATH_EXACT_F32 if fused._exact_f32 else 0)
-
-
 def _rowtile_layer(loader, ep: int, x, spec, out) -> bool:
     """A wide / max layer into `out` [N, Fo]; False (nothing launched): the
     row-tile kernel refuses the shape."""
@@ -137,19 +133,14 @@ def _rowtile_layer(loader, ep: int, x, spec, out) -> bool:
     if wl_.stride(1) != 1 or (wr_ is not None and (wr_.stride(1) != 1 or wr_.stride(0) != wl_.stride(0))):
         wl_, wr_ = wl_.contiguous(), (wr_.contiguous() if wr_ is not None else None)
     ws = fused._workspace(x.device, "sage_fwd", lib.ngnn_sage_fwd_raw_workspace_bytes(K, Fo, 0), zero=True)
-    st = _lib.stream_handle(x.device)
     seed0 = loader.batch_seed(ep, 0)
     stride = loader.batch_seed(ep, 1) - seed0
     for n, (r0, r1) in enumerate(_chunks(N, bs, max(K, Fo), f)):
         rows = r1 - r0
         rowptr, col = seed_rows(g, f, bs, seed0, stride, r0, rows)
         xrow = torch.arange(r0, r1, dtype=torch.int64, device=x.device)
-        o = out[r0:r1]
-        rc = lib.ngnn_sage_fwd_raw(
-            _lib.ptr(x), None, _lib.ptr(xrow), None, N, x.stride(0), K, rows, None, rows, None,
-            _lib.ptr(rowptr), _lib.ptr(col), _lib.ptr(col), _flags(reduce), _lib.ptr(wl_), _lib.ptr(wr_),
-            wl_.stride(0), _lib.ptr(b.detach()), Fo, _lib.ptr(o), o.stride(0), int(relu), 0.0, 0, None,
-            None, K, _lib.ptr(ws), ws.numel(), st)
+        rc = fused._fwd_raw(x, xrow=xrow, x_rows=N, n_rows=rows, rowptr=rowptr, col=col, col_x=col,
+                            reduce=reduce, wl=wl_, wr=wr_, bias=b.detach(), out=out[r0:r1], relu=relu, ws=ws)
         if rc == _lib.E_SHAPE and n == 0:
             return False
         _lib.check(rc, "ngnn_sage_fwd_raw")
@@ -187,11 +178,7 @@ def _narrow_layer(loader, ep: int, x, spec, out) -> bool:
     step = max(1, (2**31 - 4096) // (4 * max(x.stride(0), ld)))
     for n, r0 in enumerate(range(0, N, step)):
         rows = min(step, N - r0)
-        xc, oc = x[r0:r0 + rows], buf[r0:r0 + rows]
-        rc = lib.ngnn_sage_fwd_raw(
-            _lib.ptr(xc), None, None, None, 0, x.stride(0), K, rows, None, rows, None, None, None, None,
-            _flags("sum"), None, _lib.ptr(w), w.stride(0), _lib.ptr(bias), Ft, _lib.ptr(oc), ld, 0, 0.0, 0,
-            None, None, K, _lib.ptr(ws), ws.numel(), st)
+        rc = fused._fwd_raw(x[r0:r0 + rows], reduce="sum", wr=w, bias=bias, out=buf[r0:r0 + rows], ws=ws)
         if rc == _lib.E_SHAPE and n == 0:
             return False
         _lib.check(rc, "ngnn_sage_fwd_raw")

@@ -144,3 +144,25 @@ def test_sync_free_loader_contract_on_the_host():
             m(torch.zeros(8, 5), ei)
     with pytest.raises(ValueError, match="sync_free"):
         ngnn.SAGEConv(5, 4)(torch.zeros(8, 5), ei)
+
+
+def test_pad_k_ok_matches_the_row_tile_envelope():
+    """fused.pad_k_ok against a restatement of the C++ envelope rule
+    (csrc/ngnn_sage_rt.hip rt_root_image: the LDS cap 160 KiB - 1280 B, the
+    tile-count ladder, a split-bf16 image of 3 KiB per 32-column chunk and
+    16 outputs) with at most two column slices, K padded to a multiple of 4."""
+    from ngnn.fused import pad_k_ok
+
+    def rule(K, Fo):
+        K4 = (K + 3) // 4 * 4
+        chunks = (K4 + 31) // 32
+        ntw = 0
+        for c in (16, 8, 6, 4, 3, 2):
+            if c * 3 * chunks * 1024 <= 160 * 1024 - 1280:
+                ntw = c
+                break
+        return ntw > 0 and (Fo + 16 * ntw - 1) // (16 * ntw) <= 2
+
+    for Fo in (1, 16, 47, 256, 512, 1534):
+        for K in range(1, 2049):
+            assert pad_k_ok(K, Fo) == rule(K, Fo), (K, Fo)
