@@ -895,6 +895,66 @@ int ngnn_topk_rewire(const float *h, int64_t ldh, int64_t n, int64_t F, const in
                      int64_t *neg, int64_t neg_cap, int32_t *counts, int32_t *bad, int64_t *sel_out,
                      void *ws, size_t ws_bytes, void *stream);
 
+/* ----------------------------------- backward-correction and CoDi losses
+ * Added within ABI 22 (new entries only: nothing existing changed, so the
+ * version did not move).
+ *
+ * backward_correction(output, labels, C, nbr_class) of src/utils/losses.py:
+ * 51-70, given the inverse Cinv float [C, C] (row stride ldc) of its
+ * correction matrix.  With w_r = Cinv[labels[r]], p = softmax(logits[r]),
+ * q = clamp(p, 1e-5, 1 - 1e-5):
+ *   loss    = -(1 / (B C)) sum_{r < B} sum_k w_r[k] log q_rk
+ *   d x_rj  = -(g / (B C)) (w_rj m_rj - p_rj sum_k w_rk m_rk),
+ *             m_rk = [1e-5 <= p_rk <= 1 - 1e-5]  (clamp's gradient)
+ * ngnn_bc_loss_fwd writes *loss and, when dlogits is not NULL, the gradient
+ * rows [0, B) at unit scale (g = 1); ngnn_bc_loss_bwd writes them for the
+ * device scalar *grad_scale.  Rows >= B are never read or written.  One wave
+ * per row, the row partials added in a fixed order by a second launch:
+ * deterministic.  No ignore_index (the reference's scatter_ would raise): a
+ * label outside [0, C) reads no row of Cinv and makes the loss and its
+ * gradient row NaN.  ws: ngnn_bc_loss_workspace_bytes(B), 16-B aligned.
+ * Before any launch: a NULL logits / labels / Cinv / loss / ws (fwd) or
+ * grad_scale / dlogits (bwd), B or C <= 0: NGNN_E_ARG; ld, ldc or ldd < C:
+ * NGNN_E_SHAPE; B or C >= 2^31: NGNN_E_RANGE; ws too small or misaligned:
+ * NGNN_E_WORKSPACE.
+ * Replaces softmax, clamp, log, the one-hot scatter, the [B, C] x [C, C]
+ * matmul, the mean and their autograd [ext: torch]. */
+size_t ngnn_bc_loss_workspace_bytes(int64_t B);
+int ngnn_bc_loss_fwd(const float *logits, int64_t ld, int64_t B, int64_t C, const int64_t *labels,
+                     const float *Cinv, int64_t ldc, float *loss, float *dlogits, int64_t ldd,
+                     void *ws, size_t ws_bytes, void *stream);
+int ngnn_bc_loss_bwd(const float *logits, int64_t ld, int64_t B, int64_t C, const int64_t *labels,
+                     const float *Cinv, int64_t ldc, const float *grad_scale, float *dlogits,
+                     int64_t ldd, void *stream);
+
+/* CoDiLoss.forward (src/utils/losses.py:106-137): ngnn_ct_loss_fwd's exchange
+ * with the selection key
+ *   key_m[r] = l_m[r] - co_lambda * js[r],
+ *   js[r]    = sum_k mean_k (log mean_k - (lp_k + lq_k) / 2),
+ *   lp = log_softmax(y_1[r]), lq = log_softmax(y_2[r]),
+ *   mean = (softmax(y_1[r]) + softmax(y_2[r])) / 2
+ * (js_loss_compute: kl_div with target `mean` against both log-softmaxes,
+ * i.e. KL(mean || .), unbounded; a term with mean_k == 0 is 0, xlogy's rule).
+ * ind_m_sorted = argsort(key_m) ascending, ties by row index, NaN last.
+ * R = num_remember, and num_remember == 0 selects ALL B rows (R = B,
+ * losses.py:125-128).  out[0] = mean of l_1 (the cross entropy, not the key)
+ * over ind_2_sorted[:R], out[1] its mirror, out[2..3] the pure ratios over R
+ * rows, as ngnn_ct_loss_fwd.  js_out: B floats, may be NULL.  The other
+ * arguments, the B <= 8192 limit and the error codes are ngnn_ct_loss_fwd's.
+ * js is detached in the reference, so the backward is ngnn_ct_loss_bwd's on
+ * the rows the other model kept: ngnn_codi_loss_bwd, on this workspace
+ * (ngnn_codi_loss_workspace_bytes(B), kept between the forward and both
+ * backwards). */
+size_t ngnn_codi_loss_workspace_bytes(int64_t B);
+int ngnn_codi_loss_fwd(const float *y1, int64_t ld1, const float *y2, int64_t ld2, int64_t B,
+                       int64_t C, const int64_t *y_noise, int64_t ignore_index, int64_t num_remember,
+                       float co_lambda, const int64_t *ind, const uint8_t *noise_or_not,
+                       int64_t n_noise, float *out, int64_t *ind1_sorted, int64_t *ind2_sorted,
+                       float *js_out, void *ws, size_t ws_bytes, int *err, void *stream);
+int ngnn_codi_loss_bwd(int model, const float *y, int64_t ld, int64_t B, int64_t C,
+                       const int64_t *y_noise, int64_t ignore_index, const void *ws,
+                       const float *grad, float *dy, int64_t ldd, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

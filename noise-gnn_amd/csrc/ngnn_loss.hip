@@ -244,10 +244,12 @@ __device__ __forceinline__ uint32_t order_key(float f) {
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
-// workgroup m sorts model m's row losses; selects, for the OTHER model o,
-// the rows model m keeps: loss_o = mean CE of model o over them; pure_m =
-// mean noise_or_not[ind[kept_m]]
-__global__ __launch_bounds__(1024) void k_ct_select(float *__restrict__ ws, int B, int R,
+// workgroup m sorts model m's selection keys skey[m][B] (CTLoss: its row
+// losses, ws itself; CoDiLoss: CE - co_lambda * JS); selects, for the OTHER
+// model o, the rows model m keeps: loss_o = mean CE of model o over them;
+// pure_m = mean noise_or_not[ind[kept_m]]
+__global__ __launch_bounds__(1024) void k_ct_select(float *__restrict__ ws,
+                                                    const float *__restrict__ skey, int B, int R,
                                                     const int64_t *__restrict__ ind,
                                                     const uint8_t *__restrict__ clean,
                                                     int64_t n_clean, int64_t *__restrict__ ind1,
@@ -259,7 +261,7 @@ __global__ __launch_bounds__(1024) void k_ct_select(float *__restrict__ ws, int 
     const int m = blockIdx.x, o = 1 - m, tid = threadIdx.x;
     int P = 1;
     while (P < B) P <<= 1;
-    const float *l = ws + m * B;
+    const float *l = skey + m * B;
     for (int i = tid; i < P; i += 1024)
         key[i] = i < B ? (static_cast<uint64_t>(order_key(l[i])) << 32) | static_cast<uint32_t>(i)
                        : ~0ull;
@@ -342,6 +344,114 @@ __global__ __launch_bounds__(256) void k_ct_bwd(const float *__restrict__ y, int
         const float p = expf(xr[k] - lse);
         dr[k] = scale * (p - (k == c ? 1.0f : 0.0f));
     }
+}
+
+// ---------------------------------------------------------------------------
+// CoDi loss (CoDiLoss.forward, losses.py:106-137): CTLoss's exchange with the
+// selection key CE - co_lambda * JS(y_1, y_2), JS detached.  One wave takes
+// row r of BOTH models (the JS term needs both softmaxes):
+//   js[r] = sum_k mean_k (log mean_k - (lp_k + lq_k) / 2),
+//   mean = (softmax y_1 + softmax y_2) / 2  (js_loss_compute: kl_div with
+//   target mean on both sides; a term with mean_k == 0 is 0, xlogy's rule).
+// ws: CTLoss's layout (l, v, sel, cnt -- k_ct_bwd reads it as is), then the
+// keys key[2][B] from float 6 B + 4 on.
+__global__ __launch_bounds__(256) void k_codi_rows(const float *__restrict__ y1, int64_t ld1,
+                                                   const float *__restrict__ y2, int64_t ld2, int B,
+                                                   int C, const int64_t *__restrict__ t,
+                                                   int64_t ignore, float co_lambda,
+                                                   float *__restrict__ ws, float *__restrict__ skey,
+                                                   float *__restrict__ js_out) {
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= B) return;
+    const float *a = y1 + static_cast<int64_t>(r) * ld1;
+    const float *b = y2 + static_cast<int64_t>(r) * ld2;
+    const float lse1 = row_lse(a, C, lane), lse2 = row_lse(b, C, lane);
+    float js = 0.0f;
+    for (int k = lane; k < C; k += 64) {
+        const float lp = a[k] - lse1, lq = b[k] - lse2;
+        const float mean = 0.5f * (expf(lp) + expf(lq));
+        // (mean == 0: 0, not 0 * -inf; a NaN mean stays NaN)
+        if (mean != 0.0f) js += mean * (logf(mean) - 0.5f * (lp + lq));
+    }
+    js = wave_sum(js);
+    const int64_t c = t[r];
+    float l1 = 0.0f, l2 = 0.0f, v = 0.0f;
+    if (c != ignore) {
+        const bool ok = c >= 0 && c < C;  // out-of-range label: NaN, no OOB read
+        l1 = ok ? lse1 - a[c] : NAN;
+        l2 = ok ? lse2 - b[c] : NAN;
+        v = 1.0f;
+    }
+    if (lane == 0) {
+        ws[r] = l1;
+        ws[B + r] = l2;
+        ws[2 * B + r] = v;
+        ws[3 * B + r] = v;
+        skey[r] = l1 - co_lambda * js;
+        skey[B + r] = l2 - co_lambda * js;
+        if (js_out) js_out[r] = js;
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Backward loss correction (backward_correction, losses.py:51-70):
+//   loss = -(1 / (B C)) sum_r sum_k w_r[k] log q_rk,  w_r = Cinv[y_r],
+//   q = clamp(softmax(x_r), 1e-5, 1 - 1e-5)
+//   d x_rj = -(g / (B C)) (w_rj m_rj - p_rj sum_k w_rk m_rk),
+//   m_rk = [1e-5 <= p_rk <= 1 - 1e-5]  (clamp's gradient: closed interval)
+// One wave per row; part[r] = sum_k w_r[k] log q_rk (forward only), dx row r
+// (when dx is given; g NULL: unit scale).  A label outside [0, C) reads no
+// Cinv row: its partial and its gradient row are NaN.
+// (torch rounds clamp's double bounds to the tensor's float once)
+constexpr float kBcLo = static_cast<float>(1e-5), kBcHi = static_cast<float>(1.0 - 1e-5);
+
+__global__ __launch_bounds__(256) void k_bc_rows(const float *__restrict__ x, int64_t ld, int B, int C,
+                                                 const int64_t *__restrict__ y,
+                                                 const float *__restrict__ cinv, int64_t ldc,
+                                                 float *__restrict__ part, const float *__restrict__ g,
+                                                 float *__restrict__ dx, int64_t ldd) {
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= B) return;
+    const float *xr = x + static_cast<int64_t>(r) * ld;
+    const int64_t t = y[r];
+    const bool ok = t >= 0 && t < C;
+    const float *w = cinv + (ok ? t : 0) * ldc;
+    const float lse = row_lse(xr, C, lane);
+    float s = 0.0f, wm = 0.0f;
+    for (int k = lane; k < C; k += 64) {
+        const float p = expf(xr[k] - lse);
+        const float wk = ok ? w[k] : NAN;
+        s += wk * logf(p < kBcLo ? kBcLo : (p > kBcHi ? kBcHi : p));  // (a NaN passes, as clamp)
+        if (p >= kBcLo && p <= kBcHi) wm += wk;
+    }
+    s = wave_sum(s);
+    wm = wave_sum(wm);
+    if (part && lane == 0) part[r] = s;
+    if (!dx) return;
+    float *dr = dx + static_cast<int64_t>(r) * ldd;
+    const float scale = -(g ? *g : 1.0f) / (static_cast<float>(B) * static_cast<float>(C));
+    for (int k = lane; k < C; k += 64) {
+        const float p = expf(xr[k] - lse);
+        const float wk = ok ? w[k] : NAN;
+        dr[k] = scale * ((p >= kBcLo && p <= kBcHi ? wk : 0.0f) - p * wm);
+    }
+}
+
+// one workgroup adds the row partials in a fixed order -> deterministic
+__global__ __launch_bounds__(256) void k_bc_sum(const float *__restrict__ part, int B, int C,
+                                                float *__restrict__ loss) {
+    float s = 0.0f;
+    for (int i = threadIdx.x; i < B; i += 256) s += part[i];
+    __shared__ float ss[256];
+    ss[threadIdx.x] = s;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (threadIdx.x < h) ss[threadIdx.x] += ss[threadIdx.x + h];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *loss = -ss[0] / (static_cast<float>(B) * static_cast<float>(C));
 }
 
 }  // namespace
@@ -436,7 +546,7 @@ extern "C" int ngnn_ct_loss_fwd(const float *y1, int64_t ld1, const float *y2, i
                        y1, ld1, y2, ld2, (int)B, (int)C, y_noise, ignore_index, w);
     int rc = launch_status();
     if (rc) return rc;
-    hipLaunchKernelGGL(k_ct_select, dim3(2), dim3(1024), 0, st, w, (int)B, (int)num_remember, ind,
+    hipLaunchKernelGGL(k_ct_select, dim3(2), dim3(1024), 0, st, w, w, (int)B, (int)num_remember, ind,
                        noise_or_not, n_noise, ind1_sorted, ind2_sorted, out, err);
     return launch_status();
 }
@@ -451,5 +561,78 @@ extern "C" int ngnn_ct_loss_bwd(int model, const float *y, int64_t ld, int64_t B
     hipLaunchKernelGGL(k_ct_bwd, dim3(static_cast<unsigned>(ceil_div(B, 4))), dim3(256), 0,
                        as_stream(stream), y, ld, (int)B, (int)C, y_noise, ignore_index,
                        static_cast<const float *>(ws), model, grad, dy, ldd);
+    return launch_status();
+}
+
+extern "C" size_t ngnn_codi_loss_workspace_bytes(int64_t B) {
+    return B > 0 ? sizeof(float) * (8 * static_cast<size_t>(B) + 4) + 256 : 0;
+}
+
+extern "C" int ngnn_codi_loss_fwd(const float *y1, int64_t ld1, const float *y2, int64_t ld2, int64_t B,
+                                  int64_t C, const int64_t *y_noise, int64_t ignore_index,
+                                  int64_t num_remember, float co_lambda, const int64_t *ind,
+                                  const uint8_t *noise_or_not, int64_t n_noise, float *out,
+                                  int64_t *ind1_sorted, int64_t *ind2_sorted, float *js_out, void *ws,
+                                  size_t ws_bytes, int *err, void *stream) {
+    NGNN_RETURN_IF(!y1 || !y2 || !y_noise || !out || !ind1_sorted || !ind2_sorted || !ws || !err,
+                   NGNN_E_ARG);
+    NGNN_RETURN_IF(B <= 0 || C <= 0 || num_remember < 0 || num_remember > B, NGNN_E_ARG);
+    NGNN_RETURN_IF(noise_or_not && n_noise <= 0, NGNN_E_ARG);
+    NGNN_RETURN_IF(ld1 < C || ld2 < C || B > kCtMaxB, NGNN_E_SHAPE);
+    NGNN_RETURN_IF(!fits_i32(C), NGNN_E_RANGE);
+    NGNN_RETURN_IF(ws_bytes < ngnn_codi_loss_workspace_bytes(B) || !aligned(ws, 16), NGNN_E_WORKSPACE);
+    float *w = static_cast<float *>(ws);
+    float *skey = w + 6 * B + 4;
+    // an empty selection keeps every row (losses.py:125-128)
+    const int R = static_cast<int>(num_remember == 0 ? B : num_remember);
+    hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(k_codi_rows, dim3(static_cast<unsigned>(ceil_div(B, 4))), dim3(256), 0, st, y1,
+                       ld1, y2, ld2, (int)B, (int)C, y_noise, ignore_index, co_lambda, w, skey, js_out);
+    int rc = launch_status();
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_ct_select, dim3(2), dim3(1024), 0, st, w, skey, (int)B, R, ind, noise_or_not,
+                       n_noise, ind1_sorted, ind2_sorted, out, err);
+    return launch_status();
+}
+
+extern "C" int ngnn_codi_loss_bwd(int model, const float *y, int64_t ld, int64_t B, int64_t C,
+                                  const int64_t *y_noise, int64_t ignore_index, const void *ws,
+                                  const float *grad, float *dy, int64_t ldd, void *stream) {
+    // JS is detached: CTLoss's backward on the rows the other model kept
+    return ngnn_ct_loss_bwd(model, y, ld, B, C, y_noise, ignore_index, ws, grad, dy, ldd, stream);
+}
+
+extern "C" size_t ngnn_bc_loss_workspace_bytes(int64_t B) {
+    return B > 0 ? sizeof(float) * static_cast<size_t>(B) + 256 : 0;
+}
+
+extern "C" int ngnn_bc_loss_fwd(const float *logits, int64_t ld, int64_t B, int64_t C,
+                                const int64_t *labels, const float *Cinv, int64_t ldc, float *loss,
+                                float *dlogits, int64_t ldd, void *ws, size_t ws_bytes, void *stream) {
+    NGNN_RETURN_IF(!logits || !labels || !Cinv || !loss || !ws || B <= 0 || C <= 0, NGNN_E_ARG);
+    NGNN_RETURN_IF(ld < C || ldc < C || (dlogits && ldd < C), NGNN_E_SHAPE);
+    NGNN_RETURN_IF(!fits_i32(B) || !fits_i32(C), NGNN_E_RANGE);
+    NGNN_RETURN_IF(ws_bytes < ngnn_bc_loss_workspace_bytes(B) || !aligned(ws, 16), NGNN_E_WORKSPACE);
+    float *w = static_cast<float *>(ws);
+    hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(k_bc_rows, dim3(static_cast<unsigned>(ceil_div(B, 4))), dim3(256), 0, st, logits,
+                       ld, (int)B, (int)C, labels, Cinv, ldc, w, static_cast<const float *>(nullptr),
+                       dlogits, ldd);
+    int rc = launch_status();
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_bc_sum, dim3(1), dim3(256), 0, st, w, (int)B, (int)C, loss);
+    return launch_status();
+}
+
+extern "C" int ngnn_bc_loss_bwd(const float *logits, int64_t ld, int64_t B, int64_t C,
+                                const int64_t *labels, const float *Cinv, int64_t ldc,
+                                const float *grad_scale, float *dlogits, int64_t ldd, void *stream) {
+    NGNN_RETURN_IF(!logits || !labels || !Cinv || !grad_scale || !dlogits || B <= 0 || C <= 0,
+                   NGNN_E_ARG);
+    NGNN_RETURN_IF(ld < C || ldc < C || ldd < C, NGNN_E_SHAPE);
+    NGNN_RETURN_IF(!fits_i32(B) || !fits_i32(C), NGNN_E_RANGE);
+    hipLaunchKernelGGL(k_bc_rows, dim3(static_cast<unsigned>(ceil_div(B, 4))), dim3(256), 0,
+                       as_stream(stream), logits, ld, (int)B, (int)C, labels, Cinv, ldc,
+                       static_cast<float *>(nullptr), grad_scale, dlogits, ldd);
     return launch_status();
 }

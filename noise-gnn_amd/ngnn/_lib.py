@@ -126,6 +126,14 @@ SIGNATURES = {
     "ngnn_topk_rewire_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
     "ngnn_topk_rewire": (_int, [_p, _i64, _i64, _i64, _p, _p, _i64, _i64, _p, _i64, _p, _i64, _p, _p, _p,
                                 _p, _sz, _p]),
+    # (added within ABI 22: backward-correction and CoDi losses)
+    "ngnn_bc_loss_workspace_bytes": (_sz, [_i64]),
+    "ngnn_bc_loss_fwd": (_int, [_p, _i64, _i64, _i64, _p, _p, _i64, _p, _p, _i64, _p, _sz, _p]),
+    "ngnn_bc_loss_bwd": (_int, [_p, _i64, _i64, _i64, _p, _p, _i64, _p, _p, _i64, _p]),
+    "ngnn_codi_loss_workspace_bytes": (_sz, [_i64]),
+    "ngnn_codi_loss_fwd": (_int, [_p, _i64, _p, _i64, _i64, _i64, _p, _i64, _i64, ctypes.c_float, _p, _p,
+                                  _i64, _p, _p, _p, _p, _p, _sz, _p, _p]),
+    "ngnn_codi_loss_bwd": (_int, [_int, _p, _i64, _i64, _i64, _p, _i64, _p, _p, _p, _i64, _p]),
 }
 
 _lib = None

@@ -471,7 +471,9 @@ class GraphedCoTeachingStep(GraphedTrainStep):
     of the captured batch size (an epoch's last, drop_last off) runs the
     same loop body eagerly, as the reference does (num_remember of its own
     size).  Optimizers: capturable (ngnn.optim.Adam); no Adam fold (two
-    models)."""
+    models).  ``criterion`` may equally be ``ngnn.losses.CoDiLoss``
+    (``algo_type: 'codi'``, pipeline_s.py:51): the same call and 8-tuple,
+    and ``num_remember == 0`` -- one more graph key -- keeps every row."""
 
     def __init__(self, model1, optimizer1, model2, optimizer2, criterion, batch_size: int, n_cap: int,
                  e_cap: int, in_dim: int, device, noise_or_not=None, warmup: int = 3):

@@ -12,6 +12,12 @@ buffer whose rows >= batch_size stay zero (only rows < batch_size are ever
 written), and it tells the SAGE stack's backward how many leading rows can
 be nonzero (``_ngnn_nonzero_rows``), so that backward skips its row-extent
 scan.
+
+The reference's other losses follow the same plan: ``CTLoss`` and
+``CoDiLoss`` (ngnn_ct_loss_* / ngnn_codi_loss_*: both models' row losses,
+the argsorts and the exchange on the device) and ``backward_correction``
+(ngnn_bc_loss_*: loss and gradient rows in one launch pair, the inverse of
+the correction matrix kept on the device).
 """
 from __future__ import annotations
 
@@ -341,49 +347,251 @@ class CTLoss(torch.nn.Module):
         and the loss reads rows < batch_size -- the reference's
         ``model(x, ei)[:batch_size]`` without the slice (pipeline.py:113-114);
         each model's gradient then comes back [N, C], zero past the seeds."""
-        if not (y_1.is_cuda and y_2.is_cuda):
-            raise RuntimeError("ngnn.losses.CTLoss: GPU only (no CPU fallback)")
-        if y_1.dim() != 2 or y_1.shape != y_2.shape or y_1.dtype != torch.float32 \
-                or y_2.dtype != torch.float32:
-            raise ValueError("y_1, y_2 must be float32 [B, C] tensors of the same shape")
-        B, C = y_1.shape
-        if batch_size is not None:
-            if not 0 < int(batch_size) <= B:
-                raise ValueError(f"batch_size {batch_size} outside (0, {B}]")
-            B = int(batch_size)
-        dev = y_1.device
-        remember_rate = 1 - forget_rate
-        num_remember = int(remember_rate * B)  # losses.py:29-30, same float arithmetic
-        if not 0 <= num_remember <= B:
-            raise ValueError(f"forget_rate {forget_rate} gives num_remember {num_remember}")
-        a = y_1 if y_1.stride(1) == 1 else y_1.contiguous()
-        b = y_2 if y_2.stride(1) == 1 else y_2.contiguous()
-        yn = y_noise.to(device=dev, dtype=torch.int64).reshape(-1)
-        if batch_size is not None:  # (a block's labels / ids: the seed rows')
-            yn = yn[:B]
-            ind = None if ind is None else ind.reshape(-1)[:B]
-        yn = yn.contiguous()
-        if yn.numel() != B:
-            raise ValueError("y_noise must hold one label per row")
-        idx = None if ind is None else ind.to(device=dev, dtype=torch.int64).contiguous()
-        clean = None
-        if noise_or_not is not None:
-            clean = noise_or_not.to(device=dev, dtype=torch.bool).contiguous()
-        # per call (caching allocator, no sync): both backwards read it later
-        ws = torch.empty(_lib.load().ngnn_ct_loss_workspace_bytes(B), dtype=torch.uint8, device=dev)
-        out = torch.empty(4, dtype=torch.float32, device=dev)
-        i1 = torch.empty(B, dtype=torch.int64, device=dev)
-        i2 = torch.empty(B, dtype=torch.int64, device=dev)
-        err = torch.zeros(1, dtype=torch.int32, device=dev)
-        _lib.check(_lib.load().ngnn_ct_loss_fwd(
-            _lib.ptr(a), a.stride(0), _lib.ptr(b), b.stride(0), B, C, _lib.ptr(yn),
-            int(self.ignore_index), num_remember, _lib.ptr(idx), _lib.ptr(clean),
-            0 if clean is None else clean.numel(), _lib.ptr(out), _lib.ptr(i1), _lib.ptr(i2),
-            _lib.ptr(ws), ws.numel(), _lib.ptr(err), _lib.stream_handle(dev)), "ngnn_ct_loss_fwd")
+        loss_1, loss_2, out, i1, i2, num_remember, err = _exchange_forward(
+            "CTLoss", self.ignore_index, None, y_1, y_2, y_noise, forget_rate, ind, noise_or_not, batch_size)
         self.index_error = err
-        st = _CTState()
-        st.ws, st.out, st.y_noise, st.ignore, st.B, st.C = ws, out, yn, int(self.ignore_index), B, C
-        loss_1 = _CTPick.apply(a, st, 0)
-        loss_2 = _CTPick.apply(b, st, 1)
         return (loss_1, loss_2, out[2], out[3], i1[:num_remember], i2[:num_remember],
                 i1[num_remember:], i2[num_remember:])
+
+
+def _exchange_forward(name, ignore_index, co_lambda, y_1, y_2, y_noise, forget_rate, ind, noise_or_not,
+                      batch_size):
+    """The shared forward of CTLoss (co_lambda None: ngnn_ct_loss_fwd) and
+    CoDiLoss (ngnn_codi_loss_fwd): argument checks, one launch pair, the two
+    per-model autograd nodes.  Returns (loss_1, loss_2, out[4], ind_1_sorted,
+    ind_2_sorted, rows kept, index_error)."""
+    if not (y_1.is_cuda and y_2.is_cuda):
+        raise RuntimeError(f"ngnn.losses.{name}: GPU only (no CPU fallback)")
+    if y_1.dim() != 2 or y_1.shape != y_2.shape or y_1.dtype != torch.float32 \
+            or y_2.dtype != torch.float32:
+        raise ValueError("y_1, y_2 must be float32 [B, C] tensors of the same shape")
+    B, C = y_1.shape
+    if batch_size is not None:
+        if not 0 < int(batch_size) <= B:
+            raise ValueError(f"batch_size {batch_size} outside (0, {B}]")
+        B = int(batch_size)
+    dev = y_1.device
+    remember_rate = 1 - forget_rate
+    num_remember = int(remember_rate * B)  # losses.py:29-30, same float arithmetic
+    if not 0 <= num_remember <= B:
+        raise ValueError(f"forget_rate {forget_rate} gives num_remember {num_remember}")
+    a = y_1 if y_1.stride(1) == 1 else y_1.contiguous()
+    b = y_2 if y_2.stride(1) == 1 else y_2.contiguous()
+    yn = y_noise.to(device=dev, dtype=torch.int64).reshape(-1)
+    if batch_size is not None:  # (a block's labels / ids: the seed rows')
+        yn = yn[:B]
+        ind = None if ind is None else ind.reshape(-1)[:B]
+    yn = yn.contiguous()
+    if yn.numel() != B:
+        raise ValueError("y_noise must hold one label per row")
+    idx = None if ind is None else ind.to(device=dev, dtype=torch.int64).contiguous()
+    clean = None
+    if noise_or_not is not None:
+        clean = noise_or_not.to(device=dev, dtype=torch.bool).contiguous()
+    lib = _lib.load()
+    out = torch.empty(4, dtype=torch.float32, device=dev)
+    i1 = torch.empty(B, dtype=torch.int64, device=dev)
+    i2 = torch.empty(B, dtype=torch.int64, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    # workspace per call (caching allocator, no sync): both backwards read it later
+    if co_lambda is None:
+        ws = torch.empty(lib.ngnn_ct_loss_workspace_bytes(B), dtype=torch.uint8, device=dev)
+        _lib.check(lib.ngnn_ct_loss_fwd(
+            _lib.ptr(a), a.stride(0), _lib.ptr(b), b.stride(0), B, C, _lib.ptr(yn),
+            int(ignore_index), num_remember, _lib.ptr(idx), _lib.ptr(clean),
+            0 if clean is None else clean.numel(), _lib.ptr(out), _lib.ptr(i1), _lib.ptr(i2),
+            _lib.ptr(ws), ws.numel(), _lib.ptr(err), _lib.stream_handle(dev)), "ngnn_ct_loss_fwd")
+    else:
+        ws = torch.empty(lib.ngnn_codi_loss_workspace_bytes(B), dtype=torch.uint8, device=dev)
+        _lib.check(lib.ngnn_codi_loss_fwd(
+            _lib.ptr(a), a.stride(0), _lib.ptr(b), b.stride(0), B, C, _lib.ptr(yn),
+            int(ignore_index), num_remember, float(co_lambda), _lib.ptr(idx), _lib.ptr(clean),
+            0 if clean is None else clean.numel(), _lib.ptr(out), _lib.ptr(i1), _lib.ptr(i2), None,
+            _lib.ptr(ws), ws.numel(), _lib.ptr(err), _lib.stream_handle(dev)), "ngnn_codi_loss_fwd")
+        if num_remember == 0:  # an empty selection keeps every row (losses.py:125-128)
+            num_remember = B
+    st = _CTState()
+    st.ws, st.out, st.y_noise, st.ignore, st.B, st.C = ws, out, yn, int(ignore_index), B, C
+    loss_1 = _CTPick.apply(a, st, 0)
+    loss_2 = _CTPick.apply(b, st, 1)
+    return loss_1, loss_2, out, i1, i2, num_remember, err
+
+
+class CoDiLoss(torch.nn.Module):
+    """Drop-in for the reference's ``CoDiLoss(device, co_lambda)`` (losses.py:
+    72-137): CTLoss's exchange, each model's rows ranked by ``cross_entropy -
+    co_lambda * JS(y_1, y_2)`` (JS detached, ``js_loss_compute``'s form) --
+    two device launches (``ngnn_codi_loss_fwd``) instead of the softmax /
+    kl_div chain and two ``np.argsort`` host round trips; each loss's backward
+    one launch.
+
+    ``forward`` returns the reference's ``(loss_1, loss_2, pure_ratio_1,
+    pure_ratio_2, 0, 0, 0, 0)``; with ``return_indices=True`` the last four
+    are CTLoss's device index tensors (kept and forgotten rows of each
+    model).  A forget rate that remembers no row keeps ALL rows, as the
+    reference (losses.py:125-128).  Ties, ``noise_or_not``, ``index_error``,
+    ``batch_size`` and the 8192-row limit: as ``CTLoss``."""
+
+    def __init__(self, device=None, co_lambda: float = 0.1, ignore_index: int = -100,
+                 return_indices: bool = False):
+        super().__init__()
+        self.device = device
+        self.co_lambda = co_lambda
+        self.ignore_index = ignore_index
+        self.return_indices = return_indices
+        self.index_error = None
+
+    def forward(self, y_1, y_2, y_noise, forget_rate, ind, noise_or_not, batch_size: int | None = None):
+        loss_1, loss_2, out, i1, i2, kept, err = _exchange_forward(
+            "CoDiLoss", self.ignore_index, self.co_lambda, y_1, y_2, y_noise, forget_rate, ind,
+            noise_or_not, batch_size)
+        self.index_error = err
+        if not self.return_indices:
+            return loss_1, loss_2, out[2], out[3], 0, 0, 0, 0
+        return loss_1, loss_2, out[2], out[3], i1[:kept], i2[:kept], i1[kept:], i2[kept:]
+
+
+# ---------------------------------------------------------------------------
+# Backward loss correction (backward_correction, src/utils/losses.py:51-70)
+
+_cinv: dict = {}  # (id(C), device) -> (weakref to C, version, host copy or None, Cinv on the device)
+
+
+def _cinv_drop(key, _ref=None) -> None:
+    _cinv.pop(key, None)
+
+
+def _correction_inverse(C, dev) -> torch.Tensor:
+    """``np.linalg.inv(C).astype(np.float32)`` (losses.py:62) on `dev`, taken
+    once per matrix: cached by the object and the version of its contents (a
+    tensor's ``_version``; a numpy array's values, compared against a kept
+    copy -- C x C, cheaper than the inverse), dropped with the object."""
+    import numpy as np
+    key = (id(C), dev)
+    ent = _cinv.get(key)
+    is_t = torch.is_tensor(C)
+    if ent is not None and ent[0]() is C:
+        if is_t:
+            if ent[1] == C._version:
+                return ent[3]
+        elif ent[2].shape == C.shape and ent[2].dtype == C.dtype and np.array_equal(ent[2], C):
+            return ent[3]
+    host = C.detach().cpu().numpy() if is_t else np.asarray(C)
+    inv = torch.from_numpy(np.linalg.inv(host).astype(np.float32)).to(dev).contiguous()
+    try:
+        ref = weakref.ref(C, lambda _r, k=key: _cinv_drop(k))
+    except TypeError:  # (a list: no weak reference, nothing to key on)
+        return inv
+    _cinv[key] = (ref, C._version if is_t else None, None if is_t else host.copy(), inv)
+    return inv
+
+
+class _BCLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, y, cinv, batch_size: int):
+        B = int(batch_size)
+        x = logits if logits.stride(1) == 1 else logits.contiguous()
+        yy = y[:B].contiguous()
+        loss = torch.empty((), dtype=torch.float32, device=x.device)
+        lib = _lib.load()
+        ws = torch.empty(lib.ngnn_bc_loss_workspace_bytes(B), dtype=torch.uint8, device=x.device)
+        dx, ctx.hold = None, None
+        if ctx.needs_input_grad[0]:
+            # loss + the unit-scale gradient rows in the same launch
+            key = (x.device, x.size(1), ("bc", B))
+            ctx.hold = _GradHold(key, _take_grad_buffer(x.device, logits.size(0), x.size(1), ("bc", B)))
+            dx = ctx.hold.buf
+        _lib.check(lib.ngnn_bc_loss_fwd(
+            _lib.ptr(x), x.stride(0), B, x.size(1), _lib.ptr(yy), _lib.ptr(cinv), cinv.stride(0),
+            _lib.ptr(loss), _lib.ptr(dx), 0 if dx is None else dx.stride(0), _lib.ptr(ws), ws.numel(),
+            _lib.stream_handle(x.device)), "ngnn_bc_loss_fwd")
+        ctx.save_for_backward(x, yy, cinv)
+        ctx.B, ctx.n = B, logits.size(0)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        x, yy, cinv = ctx.saved_tensors
+        hold = ctx.hold
+        if hold is not None:
+            # (as _SeedXent: stream order protects the pooled buffer until this
+            # backward pass has read it)
+            dx = hold.buf[:ctx.n]
+            ctx.hold = None
+            hold.release()
+            if getattr(g, "_ngnn_unit", False):
+                dx._ngnn_nonzero_rows = ctx.B
+                return dx, None, None, None
+        else:
+            dx = _grad_buffer(x.device, ctx.n, x.size(1), ("bc", ctx.B))
+        g = g.reshape(1).to(torch.float32).contiguous()
+        _lib.check(_lib.load().ngnn_bc_loss_bwd(
+            _lib.ptr(x), x.stride(0), ctx.B, x.size(1), _lib.ptr(yy), _lib.ptr(cinv), cinv.stride(0),
+            _lib.ptr(g), _lib.ptr(dx), dx.stride(0), _lib.stream_handle(x.device)), "ngnn_bc_loss_bwd")
+        dx._ngnn_nonzero_rows = ctx.B
+        return dx, None, None, None
+
+
+class _BCLossBF16(torch.autograd.Function):
+    """backward_correction of bf16 logits, as _SeedXentBF16: the seed rows
+    widened, the fp32 kernels on them, the gradient bf16 [N, C] with rows >= B
+    zero, carrying the row hint."""
+
+    @staticmethod
+    def forward(ctx, logits, y, cinv, batch_size: int):
+        B = int(batch_size)
+        ctx.n_full = logits.size(0)
+        lw = logits if logits.stride(1) == 1 else logits.contiguous()
+        wide = torch.empty(B, lw.size(1), dtype=torch.float32, device=lw.device)
+        _lib.check(_lib.load().ngnn_widen_bf16_rows(_lib.ptr(lw), lw.stride(0), lw.size(1), B, None,
+                                                    _lib.ptr(wide), wide.stride(0),
+                                                    _lib.stream_handle(lw.device)), "ngnn_widen_bf16_rows")
+        return _BCLoss.forward(ctx, wide, y, cinv, B)
+
+    @staticmethod
+    def backward(ctx, g):
+        dx, _, _, _ = _BCLoss.backward(ctx, g)  # fp32 [B, C] (ctx.n == B there)
+        n, B, C = ctx.n_full, ctx.B, dx.size(1)
+        key = (dx.device, C, B, "bc-bf16")
+        buf = _bf16_rows.get(key)
+        if buf is None or buf.size(0) < n:
+            buf = torch.zeros(max(n, 1), C, dtype=torch.bfloat16, device=dx.device)
+            _bf16_rows[key] = buf
+        out = buf[:n]
+        d = dx[:B] if dx[:B].is_contiguous() else dx[:B].contiguous()
+        _lib.check(_lib.load().ngnn_cast_f32_bf16(_lib.ptr(d), _lib.ptr(out), B * C,
+                                                  _lib.stream_handle(d.device)), "ngnn_cast_f32_bf16")
+        out._ngnn_nonzero_rows = B
+        return out, None, None, None
+
+
+def backward_correction(output: torch.Tensor, labels: torch.Tensor, C, nbr_class: int, device=None,
+                        batch_size: int | None = None) -> torch.Tensor:
+    """Drop-in for the reference's ``backward_correction(output, labels, C,
+    nbr_class, device)`` (losses.py:51-70): ``-mean(onehot(labels) @ inv(C) *
+    log(clamp(softmax(output), 1e-5, 1 - 1e-5)))`` as two launches, its
+    gradient written by the first.  ``C`` (numpy array or tensor) is inverted
+    once and kept on the device (``_correction_inverse``).
+
+    batch_size (extension): `output` is a block's whole logits [N, C] and the
+    loss reads rows < batch_size; the gradient then comes back [N, C] from a
+    zero-row buffer, marked for the SAGE stack's bounded backward.  No
+    ignore_index (the reference's scatter_ would raise): a label outside
+    [0, nbr_class) makes the loss NaN."""
+    if not output.is_cuda:
+        raise RuntimeError("ngnn.losses.backward_correction: GPU only (no CPU fallback)")
+    if output.dim() != 2 or output.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("output must be a 2-D float32 (or bf16) tensor")
+    nc = int(nbr_class)
+    if output.size(1) != nc or tuple(C.shape) != (nc, nc):
+        raise ValueError(f"output [N, {output.size(1)}] and C {tuple(C.shape)} do not match nbr_class {nc}")
+    B = output.size(0) if batch_size is None else int(batch_size)
+    labels = labels.reshape(-1)
+    if B <= 0 or B > output.size(0) or labels.numel() < B:
+        raise ValueError("batch_size out of range")
+    if batch_size is None and labels.numel() != B:
+        raise ValueError("labels must hold one label per row")
+    cinv = _correction_inverse(C, output.device)
+    y = labels.to(device=output.device, dtype=torch.int64)
+    fn = _BCLossBF16 if output.dtype == torch.bfloat16 else _BCLoss
+    return fn.apply(output, y, cinv, B)
