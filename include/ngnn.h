@@ -955,6 +955,76 @@ int ngnn_codi_loss_bwd(int model, const float *y, int64_t ld, int64_t B, int64_t
                        const int64_t *y_noise, int64_t ignore_index, const void *ws,
                        const float *grad, float *dy, int64_t ldd, void *stream);
 
+/* ------------------------- shuffle_pos and the contrastive discriminator loss
+ * Added within ABI 22 (new entries only: nothing existing changed, so the
+ * version did not move).
+ *
+ * ngnn_shuffle_rows: shuffle_pos(features, prob) of src/utils/augmentation.py:
+ * 88-102 with m = int(F * prob) taken by the caller: per row, a uniform
+ * random m-subset of the columns, the values at those columns permuted
+ * uniformly at random.  The reference draws from torch's global CPU generator
+ * (two randperm per row); this entry defines its own draw, a pure function
+ * of (seed, row r, F, m), bitwise reproducible and independent of the launch
+ * geometry.  With mix64 the sampler's mixer (splitmix64's finaliser on
+ * z + 0x9E3779B97F4A7C15), all arithmetic modulo 2^64:
+ *   b1 = mix64(seed ^ mix64(r + 0x632BE59BD9B4E019));  key1(c) = mix64(b1 + c)
+ *   S_r = the m columns with the smallest (key1(c), c)        -- ties by column
+ *   b2 = mix64(b1 ^ 0xD1B54A32D192ED03);               key2(c) = mix64(b2 + c)
+ *   p_0 < ... < p_{m-1} the columns of S_r;
+ *   rho(j) = rank of (key2(p_j), p_j) within S_r
+ *   out[r, p_j] = x[r, p_rho(j)];  out[r, c] = x[r, c] for c not in S_r
+ * m = 0 or 1 copies, m = F permutes whole rows.  Columns [F, ldo) of out are
+ * never written, columns [F, ldx) of x never read.  out must not alias x
+ * (rows are read after other columns of them were written).  n_rows == 0 or
+ * F == 0: NGNN_OK, nothing read.  Before any launch: a negative size, m
+ * outside [0, F], a NULL x or out (with rows to move): NGNN_E_ARG; ldx or
+ * ldo < F: NGNN_E_SHAPE; n_rows >= 2^31 or F > 65535: NGNN_E_RANGE.
+ * F <= 256 (the training shapes): one wave per row; wider rows: one
+ * workgroup per row, O(F^2) key compares -- correct, not fast.  No
+ * workspace, no allocation, no host wait: safe under stream capture (which
+ * bakes `seed` in).
+ * Replaces a Python loop of two torch.randperm and an indexed write per row
+ * [ext: torch]. */
+int ngnn_shuffle_rows(const float *x, int64_t ldx, int64_t n_rows, int64_t F, int64_t m,
+                      uint64_t seed, float *out, int64_t ldo, void *stream);
+
+/* Discriminator_innerprod + BCEExeprtLoss (src/utils/data_utils.py:34-64) on
+ * the rows idx[0..M) of h, hp, hn (float [n_rows, F], row strides ldh, ldp,
+ * ldn).  With a_i = <h[idx_i], hp[idx_i]>, b_i = <h[idx_i], hn[idx_i]>:
+ *   loss = (1/M) sum_i softplus(-a_i) + (1/M) sum_i softplus(b_i)
+ *          (BCEWithLogits against ones / zeros, each a mean;
+ *           softplus(x) = max(x, 0) + log1p(exp(-|x|)))
+ *   d h [idx_i] += (g/M) (-sigma(-a_i) hp[idx_i] + sigma(b_i) hn[idx_i])
+ *   d hp[idx_i] += (g/M) (-sigma(-a_i)) h[idx_i]
+ *   d hn[idx_i] += (g/M)   sigma(b_i)   h[idx_i]
+ * ngnn_contrast_fwd writes out[0] = loss, out[1] / out[2] = its positive /
+ * negative term and keeps a_i, b_i in ws (ngnn_contrast_workspace_bytes(M),
+ * 16-B aligned, kept until the backward; the logits are accumulated and kept
+ * in double: e^-a carries a's absolute error); one wave per selected row, the row
+ * terms added in a fixed order by a second launch: deterministic.
+ * ngnn_contrast_bwd ADDS the gradient rows, scaled by the device scalar
+ * *grad_scale, with float atomics into the buffers the caller prepared (any
+ * of dh, dhp, dhn may be NULL): duplicates in idx accumulate, as
+ * index_put_(accumulate=True); distinct indices give a bitwise reproducible
+ * result.  sigma(-a) is evaluated as 1 / (1 + e^a), so the positive term's
+ * gradient survives large logits (torch's fp32 BCEWithLogits backward returns
+ * 0 there from a ~ 17 on).  An idx entry outside [0, n_rows) reads and writes
+ * nothing, makes the loss NaN and adds 1 to *bad (may be NULL); the
+ * reference raises there.  Before any launch: a NULL h / hp / hn / idx / ws /
+ * out (fwd) / grad_scale (bwd), n_rows, F or M <= 0: NGNN_E_ARG; a row
+ * stride < F: NGNN_E_SHAPE; n_rows, F or M >= 2^31: NGNN_E_RANGE; ws too
+ * small or misaligned (fwd): NGNN_E_WORKSPACE.
+ * Replaces three index_select, two mul + sum, two BCEWithLogitsLoss and
+ * three zero-filled [n_rows, F] index backward gradients [ext: torch]. */
+size_t ngnn_contrast_workspace_bytes(int64_t M);
+int ngnn_contrast_fwd(const float *h, int64_t ldh, const float *hp, int64_t ldp, const float *hn,
+                      int64_t ldn, int64_t n_rows, int64_t F, const int64_t *idx, int64_t M,
+                      float *out, int32_t *bad, void *ws, size_t ws_bytes, void *stream);
+int ngnn_contrast_bwd(const float *h, int64_t ldh, const float *hp, int64_t ldp, const float *hn,
+                      int64_t ldn, int64_t n_rows, int64_t F, const int64_t *idx, int64_t M,
+                      const void *ws, const float *grad_scale, float *dh, int64_t lddh, float *dhp,
+                      int64_t lddp, float *dhn, int64_t lddn, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,7 +9,7 @@ from . import _lib
 from .block import Block, get_block
 from .models import NGNN, SAGE, SAGEPL, SimpleGCN
 from .nn import GCNConv, Linear, SAGEConv
-from .ops import add_node_noise, segment_aggregate, topk_rewire
+from .ops import add_node_noise, segment_aggregate, shuffle_pos, topk_rewire
 
 __all__ = ["Block", "get_block", "NGNN", "SAGE", "SAGEPL", "SimpleGCN", "GCNConv", "Linear", "SAGEConv",
-           "add_node_noise", "segment_aggregate", "topk_rewire", "_lib"]
+           "add_node_noise", "segment_aggregate", "shuffle_pos", "topk_rewire", "_lib"]

@@ -134,6 +134,12 @@ SIGNATURES = {
     "ngnn_codi_loss_fwd": (_int, [_p, _i64, _p, _i64, _i64, _i64, _p, _i64, _i64, ctypes.c_float, _p, _p,
                                   _i64, _p, _p, _p, _p, _p, _sz, _p, _p]),
     "ngnn_codi_loss_bwd": (_int, [_int, _p, _i64, _i64, _i64, _p, _i64, _p, _p, _p, _i64, _p]),
+    # (added within ABI 22: shuffle_pos and the contrastive discriminator loss)
+    "ngnn_shuffle_rows": (_int, [_p, _i64, _i64, _i64, _i64, ctypes.c_uint64, _p, _i64, _p]),
+    "ngnn_contrast_workspace_bytes": (_sz, [_i64]),
+    "ngnn_contrast_fwd": (_int, [_p, _i64, _p, _i64, _p, _i64, _i64, _i64, _p, _i64, _p, _p, _p, _sz, _p]),
+    "ngnn_contrast_bwd": (_int, [_p, _i64, _p, _i64, _p, _i64, _i64, _i64, _p, _i64, _p, _p, _p, _i64, _p,
+                                 _i64, _p, _i64, _p]),
 }
 
 _lib = None

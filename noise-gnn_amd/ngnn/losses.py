@@ -17,7 +17,10 @@ The reference's other losses follow the same plan: ``CTLoss`` and
 ``CoDiLoss`` (ngnn_ct_loss_* / ngnn_codi_loss_*: both models' row losses,
 the argsorts and the exchange on the device) and ``backward_correction``
 (ngnn_bc_loss_*: loss and gradient rows in one launch pair, the inverse of
-the correction matrix kept on the device).
+the correction matrix kept on the device), and so does the contrastive term
+of the reference's train_ct step, ``contrastive_loss`` (ngnn_contrast_*:
+``Discriminator_innerprod`` + ``BCEExeprtLoss`` on the rows an index tensor
+names, one launch pair each way).
 """
 from __future__ import annotations
 
@@ -595,3 +598,178 @@ def backward_correction(output: torch.Tensor, labels: torch.Tensor, C, nbr_class
     y = labels.to(device=output.device, dtype=torch.int64)
     fn = _BCLossBF16 if output.dtype == torch.bfloat16 else _BCLoss
     return fn.apply(output, y, cinv, B)
+
+
+# ---------------------------------------------------------------------------
+# Contrastive discriminator loss (Discriminator_innerprod + BCEExeprtLoss,
+# src/utils/data_utils.py:34-64)
+
+_bad_index_counters: dict = {}  # device index -> int32[1] on that device
+
+
+def _bad_index_counter(device: torch.device) -> torch.Tensor:
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    c = _bad_index_counters.get(idx)
+    if c is None:
+        c = _bad_index_counters[idx] = torch.zeros(1, dtype=torch.int32, device=torch.device("cuda", idx))
+    return c
+
+
+def contrast_bad_indices(device=None, reset: bool = False) -> int:
+    """How many ``index`` entries ``contrastive_loss`` met on ``device`` outside
+    its rows (each makes that call's loss NaN).  Debugging only: reading the
+    device counter synchronises (``contrastive_loss.bad_index`` is the counter
+    itself, a device tensor)."""
+    c = _bad_index_counter(torch.device("cuda" if device is None else device))
+    n = int(c.item())
+    if reset:
+        c.zero_()
+    return n
+
+
+class _Contrast(torch.autograd.Function):
+    """ngnn_contrast_fwd / _bwd.  B None: the gradients are fresh [N, H] zero
+    tensors.  B given: each needed gradient is a zero-row buffer taken at
+    forward time for this node alone (two contrastive terms pending in one
+    step, one per model, get different buffers), its B leading rows cleared
+    on the stream before the scatter."""
+
+    @staticmethod
+    def forward(ctx, h, hp, hn, index, B):
+        dev = h.device
+        N, H = h.shape
+        rows = N if B is None else B
+        M = index.numel()
+        lib = _lib.load()
+        out = torch.empty(3, dtype=torch.float32, device=dev)
+        ws = torch.empty(lib.ngnn_contrast_workspace_bytes(M), dtype=torch.uint8, device=dev)
+        bad = _bad_index_counter(dev)
+        _lib.check(lib.ngnn_contrast_fwd(
+            _lib.ptr(h), h.stride(0), _lib.ptr(hp), hp.stride(0), _lib.ptr(hn), hn.stride(0), rows, H,
+            _lib.ptr(index), M, _lib.ptr(out), _lib.ptr(bad), _lib.ptr(ws), ws.numel(),
+            _lib.stream_handle(dev)), "ngnn_contrast_fwd")
+        ctx.holds = [None, None, None]
+        if B is not None:
+            key = (dev, H, ("contrast", B))
+            for k in range(3):
+                if ctx.needs_input_grad[k]:
+                    ctx.holds[k] = _GradHold(key, _take_grad_buffer(dev, N, H, ("contrast", B)))
+        ctx.save_for_backward(h, hp, hn, index)
+        ctx.ws, ctx.B, ctx.rows = ws, B, rows
+        return out[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        h, hp, hn, index = ctx.saved_tensors
+        dev = h.device
+        N, H = h.shape
+        grads = [None, None, None]
+        for k in range(3):
+            if not ctx.needs_input_grad[k]:
+                continue
+            hold = ctx.holds[k]
+            if hold is None:
+                grads[k] = torch.zeros(N, H, dtype=torch.float32, device=dev)
+            else:
+                # back to the pool: stream order protects the rows until this
+                # backward pass has consumed them (as _SeedXent)
+                d = hold.buf[:N]
+                ctx.holds[k] = None
+                hold.release()
+                d[:ctx.B].zero_()
+                d._ngnn_nonzero_rows = ctx.B  # rows >= B are zero: the SAGE backward's row bound
+                grads[k] = d
+        g = g.reshape(1).to(torch.float32).contiguous()
+        dh, dp, dn = grads
+        _lib.check(_lib.load().ngnn_contrast_bwd(
+            _lib.ptr(h), h.stride(0), _lib.ptr(hp), hp.stride(0), _lib.ptr(hn), hn.stride(0), ctx.rows, H,
+            _lib.ptr(index), index.numel(), _lib.ptr(ctx.ws), _lib.ptr(g),
+            _lib.ptr(dh), 0 if dh is None else dh.stride(0), _lib.ptr(dp), 0 if dp is None else dp.stride(0),
+            _lib.ptr(dn), 0 if dn is None else dn.stride(0), _lib.stream_handle(dev)), "ngnn_contrast_bwd")
+        return dh, dp, dn, None, None
+
+
+def contrastive_loss(h: torch.Tensor, h_pos: torch.Tensor, h_neg: torch.Tensor, index: torch.Tensor,
+                     batch_size: int | None = None) -> torch.Tensor:
+    """``BCEExeprtLoss(n)(*Discriminator_innerprod()(h[index], h_pos[index],
+    h_neg[index]))`` of the reference's train_ct step (pipeline_test.py:
+    150-158) as one launch pair each way (``ngnn_contrast_fwd`` / ``_bwd``):
+    ``mean softplus(-<h_i, h_pos_i>) + mean softplus(<h_i, h_neg_i>)`` over the
+    rows ``index`` (a device int64 tensor, e.g. ``CTLoss``'s ``ind_noisy_m``),
+    with no gathered copies and no ``[N, H]`` index-backward zero fills beyond
+    the gradients themselves.  Deterministic forward; the backward adds with
+    float atomics (duplicates accumulate as ``index_put_(accumulate=True)``;
+    distinct indices: bitwise reproducible) and keeps the positive term's
+    gradient at large logits, where torch's fp32 ``BCEWithLogitsLoss`` backward
+    returns 0.
+
+    batch_size=B (extension): the caller promises every index is < B (seed
+    rows); each gradient is then a zero-row buffer whose B leading rows are
+    cleared and scattered into, marked for the SAGE stack's bounded backward
+    (``_ngnn_nonzero_rows``), and an index >= B counts as bad.  A bad index
+    reads and writes nothing, makes the loss NaN and is counted on the device
+    (``contrastive_loss.bad_index``: the int32 counter tensor, no sync;
+    ``contrast_bad_indices()`` reads it).  No rows (``index`` empty): NaN, the
+    reference's mean over nothing, without a launch.  fp32, GPU only."""
+    for name, t in (("h", h), ("h_pos", h_pos), ("h_neg", h_neg)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"ngnn.losses.contrastive_loss: GPU only (no CPU fallback): {name}")
+    if h.dim() != 2 or h.shape != h_pos.shape or h.shape != h_neg.shape:
+        raise ValueError("h, h_pos, h_neg must be [N, H] tensors of the same shape")
+    if not (h.dtype == h_pos.dtype == h_neg.dtype == torch.float32):
+        raise TypeError("contrastive_loss: only float32 is supported")
+    if not isinstance(index, torch.Tensor) or not index.is_cuda or index.dtype != torch.int64:
+        raise ValueError("contrastive_loss: index must be a device int64 tensor")
+    N, H = h.shape
+    if batch_size is not None:
+        batch_size = int(batch_size)
+        if not 0 < batch_size <= N:
+            raise ValueError(f"batch_size {batch_size} outside (0, {N}]")
+    contrastive_loss.bad_index = _bad_index_counter(h.device)
+    index = index.reshape(-1).contiguous()
+    if H == 0:
+        raise ValueError("contrastive_loss: H must be positive")
+    if index.numel() == 0:  # (the entries refuse M == 0)
+        return torch.full((), float("nan"), dtype=torch.float32, device=h.device)
+    a, p, n = (t if t.stride(1) == 1 and t.stride(0) >= H else t.contiguous() for t in (h, h_pos, h_neg))
+    return _Contrast.apply(a, p, n, index, batch_size)
+
+
+contrastive_loss.bad_index = None
+
+
+class Discriminator_innerprod(torch.nn.Module):
+    """Drop-in for the reference's ``Discriminator_innerprod()``
+    (data_utils.py:53-64): ``forward(H, Hp1, Hn)`` -> the two ``[M, 1]`` logit
+    columns ``sum(H * Hp1, 1)`` and ``sum(H * Hn, 1)``.  Kept so that the
+    reference's two-step call (gather, discriminate, ``BCEExeprtLoss``) runs
+    unchanged; it is the torch composition on the device.  The fused path,
+    which takes the row indices instead of gathered copies, is
+    ``contrastive_loss``."""
+
+    def forward(self, H, Hp1, Hn):
+        if not (H.is_cuda and Hp1.is_cuda and Hn.is_cuda):
+            raise RuntimeError("ngnn.losses.Discriminator_innerprod: GPU only (no CPU fallback)")
+        logits_pa = torch.sum(torch.mul(H, Hp1), dim=1, keepdim=True)
+        logits_n = torch.sum(torch.mul(H, Hn), dim=1, keepdim=True)
+        return logits_pa, logits_n
+
+
+class BCEExeprtLoss(torch.nn.Module):
+    """Drop-in for the reference's ``BCEExeprtLoss(nbr_nodes)`` (data_utils.py:
+    34-50; the name is the reference's spelling): ``forward(logits_p1,
+    logits_n)`` -> ``BCEWithLogits(logits_p1, 1) + BCEWithLogits(logits_n, 0)``,
+    each a mean, written as ``mean softplus(-p) + mean softplus(n)`` (the same
+    value; its backward keeps sigma(-p) at large p).  The second half of the
+    two-step call; the fused path is ``contrastive_loss``."""
+
+    def __init__(self, nbr_nodes=None):
+        super().__init__()
+        self.nbr_nodes = nbr_nodes
+
+    def forward(self, logits_p1, logits_n):
+        if not (logits_p1.is_cuda and logits_n.is_cuda):
+            raise RuntimeError("ngnn.losses.BCEExeprtLoss: GPU only (no CPU fallback)")
+        pos = torch.squeeze(logits_p1)
+        neg = torch.squeeze(logits_n)
+        return torch.nn.functional.softplus(-pos).mean() + torch.nn.functional.softplus(neg).mean()

@@ -334,3 +334,43 @@ def topk_rewire(h: torch.Tensor, edge_index: torch.Tensor, device=None, k_percen
                              "similarity of a selection's threshold (include/ngnn.h)")
     out = (pos[:, :n_pos].contiguous(), neg[:, :n_neg].contiguous())
     return out + (sel,) if return_selections else out
+
+
+# ---- per-row partial feature shuffle (ngnn_shuffle_rows) ----
+
+def shuffle_pos(features: torch.Tensor, device=None, prob: float = 0.1, seed: int | None = None) -> torch.Tensor:
+    """The reference's ``shuffle_pos(features, device, prob)``
+    (``src/utils/augmentation.py:88-102``): in every row, ``m = int(F * prob)``
+    columns drawn uniformly at random trade their values by a uniform random
+    permutation; the other columns are copied.  One launch
+    (``ngnn_shuffle_rows``) instead of a Python loop of two ``torch.randperm``
+    and an indexed write per row.  Returns a new detached tensor, as the
+    reference's ``clone().detach()``; row-strided views are read in place.
+
+    The draw is this library's own (include/ngnn.h), a pure function of
+    ``(seed, row, F, m)`` -- the reference's depends on torch's global CPU
+    generator and cannot be reproduced.  ``seed=None`` draws a 62-bit seed
+    from torch's default CPU generator (a host-only call, no device sync), so
+    ``torch.manual_seed`` makes a run repeatable.  A captured graph bakes in
+    the seed it was captured with: every replay shuffles the same way.
+    ``device`` is accepted for the reference's signature and ignored (the
+    result stays on ``features``' device).  fp32, GPU only."""
+    if not isinstance(features, torch.Tensor) or not features.is_cuda:
+        raise RuntimeError("ngnn runs on the GPU only: shuffle_pos's features are on the CPU")
+    if features.dim() != 2:
+        raise ValueError(f"shuffle_pos: features must be 2-D [N, F], got shape {tuple(features.shape)}")
+    if features.dtype != torch.float32:
+        raise TypeError(f"shuffle_pos: only float32 features are supported, got {features.dtype}")
+    x = _row_major(features.detach())
+    N, F = x.shape
+    m = int(F * prob)  # augmentation.py:94, same float arithmetic
+    if not 0 <= m <= F:
+        raise ValueError(f"shuffle_pos: prob {prob} moves {m} of {F} columns")
+    if seed is None:
+        seed = int(torch.randint(0, 1 << 62, (1,)).item())
+    out = torch.empty(N, F, dtype=torch.float32, device=x.device)
+    with _timing.span("shuffle_pos", 2 * N * F * 4):
+        rc = _lib.load().ngnn_shuffle_rows(_lib.ptr(x), _ld(x), N, F, m, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                           _lib.ptr(out), F, _lib.stream_handle(x.device))
+    _lib.check(rc, "ngnn_shuffle_rows")
+    return out
