@@ -39,9 +39,24 @@
 // exact) into the fp32 accumulators.  dh = X W1 sums over F1, so its scales
 // are X's chunk scale and the wave's W1 slice scale; dz0 is scaled by the
 // bound 96 2^30 yscale of |dh| in those units (a constant shift, e_dz).
+//
+// Chunks and dy: dy is zero past the seed rows, so only the first ceil(R / 32)
+// chunks (the seed chunks) hold any.  A row slice owns every S-th chunk (s,
+// s + S, ...), which deals the seed chunks over the slices, and a chunk
+// without dy skips the dy loads, their share of X's maximum, their split and
+// LDS stores, db1's sum, stage B's dy-only k-chunk and the dW_r1 products.
+//  * For finite inputs the skipping leaves every accumulator as it was: the
+//    skipped products are exact zeros added to a +0 or non-zero sum, and X's
+//    maximum is unchanged because dy was 0 there.
+//  * The cyclic ownership changes which rows each slab sums, so the fp32
+//    summation order differs from a contiguous split: rounding only, inside
+//    the 1e-5 bars.  Two launches still agree bit for bit.
+//  * Non-finite h or W_r1 against the zero dy of rows >= R no longer gives
+//    NaN in dW_r1 or dh: those products are not formed.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <type_traits>
 
 #include "ngnn_device.h"
 
@@ -157,7 +172,8 @@ __device__ __forceinline__ float sum_xor32(float v) {
 // (rt = w >> 2, nt = w & 3) -> dh rows 16 rt .. + 15, columns 16 nt .. + 15 of
 // the chunk.  Stage C0: wave (mat = w >> 2, nt) -> dW_r0 (mat 0, B = x) or
 // dW_l0 (mat 1, B = agg0) rows n of tile nt, all K0 columns.  Stage C1: wave
-// w -> 3 of the 24 [dW_r1; dW_l1] tiles (6 f-tiles x 4 n-tiles).
+// w -> tiles w, w + 8, w + 16 of the 24 [dW_r1; dW_l1] tiles (6 f-tiles x 4
+// n-tiles): both kinds on every wave.
 // KT: 16-column tiles of K0 computed (past K0 the images hold zeros)
 // LAG: a chunk's maxima published at the barrier that ends the previous chunk
 // (its loads waited for right after stage B) -- else after stage C, at a
@@ -191,8 +207,10 @@ __global__ __launch_bounds__(B2_THREADS, 1) void k_bwd2(B2Args a) {
     const int Rn = max(R, min(a.n_rows, *a.rn_ptr));
     const int S = a.S;
     const int C = (Rn + B2_ROWS - 1) / B2_ROWS;  // chunks below Rn
-    const int cb = static_cast<int>(static_cast<int64_t>(s) * C / S);
-    const int ce = static_cast<int>(static_cast<int64_t>(s + 1) * C / S);
+    // slice s owns chunks s, s + S, s + 2 S, ... < C; the seed chunks (those
+    // with a dy row: c < Cs) are the first ones, so they spread over the
+    // slices -- a chunk past them has no dy and skips everything dy feeds
+    const int Cs = (R + B2_ROWS - 1) / B2_ROWS;
     const int K0 = a.K0, F1 = a.F1;
 
     // ---- stage-B operand: [W_r1; W_l1] rows k = 32 kc + 8 q + j (W_r1 rows
@@ -266,16 +284,21 @@ __global__ __launch_bounds__(B2_THREADS, 1) void k_bwd2(B2Args a) {
     const uint32_t C44 = static_cast<uint32_t>(a.C4) * 4u;
     auto iload = [&](int c) __attribute__((always_inline)) -> int {  // low word of n_id
         const int r = c * B2_ROWS + rx;
-        return buf_load1i(ir, (c < ce && r < Rn) ? 8 * r : kOOB, 0, 0);
+        return buf_load1i(ir, (c < C && r < Rn) ? 8 * r : kOOB, 0, 0);
     };
+    // (the slice's next chunk is c + S; dyv is loaded, and read, on seed
+    // chunks only)
     auto load = [&](int c, Pre &p) __attribute__((always_inline)) {
         const int r0 = c * B2_ROWS;
-        const bool live = c < ce;
+        const bool live = c < C;
+        if (c < Cs) {
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int lr = rd + 10 * u, r = r0 + lr;
-            const bool ok = live && t < 480 && lr < B2_ROWS && r < R && fd < F1;
-            p.dyv[u] = buf_load1(dyr, ok ? static_cast<int>(static_cast<uint32_t>(r) * ldy4) + 4 * fd : kOOB, 0, 0);
+            for (int u = 0; u < 4; ++u) {
+                const int lr = rd + 10 * u, r = r0 + lr;
+                const bool ok = t < 480 && lr < B2_ROWS && r < R && fd < F1;
+                p.dyv[u] =
+                    buf_load1(dyr, ok ? static_cast<int>(static_cast<uint32_t>(r) * ldy4) + 4 * fd : kOOB, 0, 0);
+            }
         }
         {
             const int r = r0 + rg;
@@ -292,7 +315,7 @@ __global__ __launch_bounds__(B2_THREADS, 1) void k_bwd2(B2Args a) {
             const bool okr = live && r < Rn;
             // (XR: this chunk's n_id word arrived a chunk ago)
             const uint32_t xr = (XR && xrow) ? static_cast<uint32_t>(p.xi) : static_cast<uint32_t>(r);
-            if (XR) p.xi = iload(c + 1);
+            if (XR) p.xi = iload(c + S);
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 const int k = 8 * cx + 4 * u;
@@ -315,10 +338,12 @@ __global__ __launch_bounds__(B2_THREADS, 1) void k_bwd2(B2Args a) {
     // read 0; edgeless rows' aggregate counts as 0), wave-reduced, into LDS
     // slot sl (8 waves x 4); every thread reads them back after a barrier
     float4 *smax = reinterpret_cast<float4 *>(sred + 2 * 256 + 480);  // [2][8]
-    auto publish_max = [&](const auto &p, int sl) __attribute__((always_inline)) {
+    // (hd: the chunk has dy rows -- past them dy is 0 and X's maximum is g's)
+    auto publish_max = [&](const auto &p, int sl, bool hd) __attribute__((always_inline)) {
         if (DBG & 1) return;
-        float mX = fmaxf(amax4(p.gv), fmaxf(fmaxf(fabsf(p.dyv[0]), fabsf(p.dyv[1])),
-                                          fmaxf(fabsf(p.dyv[2]), fabsf(p.dyv[3]))));
+        float mX = amax4(p.gv);
+        if (hd)
+            mX = fmaxf(mX, fmaxf(fmaxf(fabsf(p.dyv[0]), fabsf(p.dyv[1])), fmaxf(fabsf(p.dyv[2]), fabsf(p.dyv[3]))));
         float mH = amax4(p.hv);
         float mx = fmaxf(amax4(p.xv[0]), amax4(p.xv[1]));
         float ma = p.d1 > p.d0 ? fmaxf(amax4(p.av[0]), amax4(p.av[1])) : 0.0f;
@@ -379,9 +404,17 @@ __global__ __launch_bounds__(B2_THREADS, 1) void k_bwd2(B2Args a) {
         *reinterpret_cast<__attribute__((address_space(3))) bf4 *>(img + part_stride + off) = p2;
     };
     float d1acc = 0.0f;  // db1 partial: column fd, rows of this thread
-    auto stage_images = [&](const Pre &p, L16 *buf, const Exps &e) __attribute__((always_inline)) {
+    // hd: the chunk has dy rows.  Without them X's dy columns are not
+    // written: nothing reads columns 0..31 of such a chunk, and columns
+    // 32..47 (stage B's k-chunk 1 holds them next to g) are zeroed when the
+    // buffer last held a seed chunk or nothing yet (zx)
+    auto stage_images = [&](const Pre &p, L16 *buf, const Exps &e, bool hd, bool zx) __attribute__((always_inline)) {
         L16 *ix = buf, *ih = ix + IMG_X, *ik = ih + IMG_H, *ia = ik + IMG_K;
-        if (t < 480) {
+        if (zx) {  // 32 rows x 2 parts x 8 column pairs, 4 B per thread
+            L16 *z = ix + ((t >> 3) & 1) * B2_ROWS * XS + (t >> 4) * XS + 32 + 2 * (t & 7);
+            *reinterpret_cast<__attribute__((address_space(3))) int *>(z) = 0;
+        }
+        if (hd && t < 480) {
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int lr = rd + 10 * u;
@@ -404,17 +437,21 @@ __global__ __launch_bounds__(B2_THREADS, 1) void k_bwd2(B2Args a) {
 
     // ---- stage B: dh tile (rt, nt) -> masked dz0 parts into sA
     float d0acc = 0.0f;  // db0 partial: column 16 nt + l16, rows 16 rt + 4 q + i
-    auto stage_b = [&](L16 *buf, const Exps &e) __attribute__((always_inline)) {
+    // (k-chunk 0 is dy columns 0..31 only: skipped on a chunk without dy, as
+    // the root-free form skips it everywhere -- exact zeros either way)
+    auto stage_b = [&](L16 *buf, const Exps &e, bool hd) __attribute__((always_inline)) {
         const L16 *ix = buf, *ih = ix + IMG_X;
         L16 *sa = buf + IMG_X + IMG_H + 2 * IMG_K;
         v4f acc{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kc = ROOT ? 0 : 1; kc < 3; ++kc) {
+        auto kstep = [&](int kc) __attribute__((always_inline)) {
             const int off = (16 * rt + l16) * XS + 32 * kc + 8 * q;
             const bf8 a1 = *reinterpret_cast<const __attribute__((address_space(3))) bf8 *>(ix + off);
             const bf8 a2 = *reinterpret_cast<const __attribute__((address_space(3))) bf8 *>(ix + B2_ROWS * XS + off);
             acc = mfma3(a1, a2, wb[kc][0], wb[kc][1], acc);
-        }
+        };
+        if (ROOT && hd) kstep(0);
+        kstep(1);
+        kstep(2);
         // mask: the sign of h's first part (a positive h below 2^-39 of its
         // chunk's max rounds to +0 -- a pre-activation that far inside fp32's
         // noise of the ReLU kink)
@@ -441,27 +478,43 @@ __global__ __launch_bounds__(B2_THREADS, 1) void k_bwd2(B2Args a) {
 
     // ---- stage C: the weight-gradient products of one staged chunk
     // ROOT: wave (mat, nt) takes dW_r0 (mat 0) or dW_l0 (mat 1) rows of
-    // n-tile nt over all KT column tiles, and tiles 3 wv + u of the 24 of
-    // [dW_r1; dW_l1]; root-free: dW_l0 column tiles kt = (wv >> 2) + 2 i, and
-    // tiles wv + 8 u of the 12 of dW_l1 (f-tiles 3..5)
+    // n-tile nt over all KT column tiles, and tiles wv + 8 u of the 24 of
+    // [dW_r1; dW_l1] (tile tt = 4 mf + nn: f-tile mf = mat + 2 u, n-tile nn =
+    // nt for all three, so one h fragment serves them).  Tiles 0..11 are
+    // dW_r1, 12..23 dW_l1: waves 0-3 hold 2 + 1 of them, waves 4-7 1 + 2, and
+    // a chunk without dy costs a wave its dW_l1 tiles only.  Root-free: dW_l0
+    // column tiles kt = (wv >> 2) + 2 i, and tiles wv + 8 u of the 12 of
+    // dW_l1 (f-tiles 3..5)
     constexpr int NK0 = ROOT ? KT : (KT + 1) / 2;
     constexpr int NC1 = ROOT ? 3 : 2;
     constexpr int C1_TILES = 24;
     const int mat = wv >> 2;
     auto c0_kt = [&](int i) { return ROOT ? i : mat + 2 * i; };
-    auto c1_tile = [&](int u) { return ROOT ? 3 * wv + u : (wv + 8 * u < 12 ? 12 + wv + 8 * u : C1_TILES); };
+    auto c1_tile = [&](int u) { return ROOT ? wv + 8 * u : (wv + 8 * u < 12 ? 12 + wv + 8 * u : C1_TILES); };
     v4f acc0[NK0], acc1[NC1];
 #pragma unroll
     for (int i = 0; i < NK0; ++i) acc0[i] = v4f{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int i = 0; i < NC1; ++i) acc1[i] = v4f{0.f, 0.f, 0.f, 0.f};
     // the accumulators hold sums in the units of the last chunk added:
-    // 2^E0 (dz0 2^(eX + eW - e_dz) times x / agg0 2^(ex | ea)), 2^E1 (X 2^eX
-    // times h 2^eH); each chunk rescales them by the change (v_ldexp, exact
-    // unless a sum falls below fp32's range) and its MFMAs accumulate on top
-    int E0 = 0, E1 = 0;
+    // 2^E0 (dz0 2^(eX + eW - e_dz) times x / agg0 2^(ex | ea)), 2^E1[u] (X
+    // 2^eX times h 2^eH); each chunk rescales them by the change (v_ldexp,
+    // exact unless a sum falls below fp32's range) and its MFMAs accumulate
+    // on top.  A dW_r1 tile is rescaled, and its exponent moved, on seed
+    // chunks only.  Those are the first chunks of the slice's sequence, one
+    // after the other, so its exponent too moves by one chunk-to-chunk step
+    // at a time -- at most 2^20 per operand, read_exps' clamp -- and after
+    // the last seed chunk the tile rests until the final unscaling.
+    int E0 = 0, E1[NC1] = {};
     bool acc_empty = true;
-    auto stage_c = [&](const L16 *buf, const Exps &e) __attribute__((always_inline)) {
+    // HD: the chunk has dy rows (compile time: one straight-line body each)
+    auto stage_c = [&](const L16 *buf, const Exps &e, auto hd_c) __attribute__((always_inline)) {
+        constexpr bool HD = decltype(hd_c)::value;
+        // (a rooted wave's tile 0 is dW_r1, tile 2 dW_l1, tile 1 by its half)
+        auto c1_on = [&](int u) {
+            if (!ROOT) return c1_tile(u) < C1_TILES;
+            return HD || u == 2 || (u == 1 && mat);
+        };
         const L16 *ix = buf, *ih = ix + IMG_X, *ik = ih + IMG_H, *ia = ik + IMG_K;
         const L16 *sa = ia + IMG_K;
         // C0: A = dz0^T of n-tile nt (both row tiles), B = x / agg0 tiles
@@ -470,39 +523,47 @@ __global__ __launch_bounds__(B2_THREADS, 1) void k_bwd2(B2Args a) {
         const L16 *img = (mat || !ROOT) ? ia : ik;
         // every fragment read of the stage issued before its first MFMA (the
         // reads' latency once per chunk, not once per tile)
-        bf8 b1[KT], b2[KT], x1[3], x2[3], h1[3], h2[3];
+        bf8 b1[KT], b2[KT], x1[3], x2[3];
 #pragma unroll
         for (int i = 0; i < NK0; ++i) {
             const int kt = c0_kt(i);
             b1[i] = tr_frag(img, KS, 16 * kt, ln);
             b2[i] = tr_frag(img + B2_ROWS * KS, KS, 16 * kt, ln);
         }
-        // C1: tiles of [dW_r1; dW_l1] (f-tile mf, n-tile nn): A = X^T, B = h
+        // C1: tiles of [dW_r1; dW_l1] (f-tile mf, n-tile nt): A = X^T, B = h
+        // (X's dy columns, f-tiles 0..2, are read on seed chunks only)
+        const bf8 h1 = tr_frag(ih, HS, 16 * nt, ln), h2 = tr_frag(ih + B2_ROWS * HS, HS, 16 * nt, ln);
 #pragma unroll
-        for (int u = 0; u < NC1; ++u) {
-            const int tt = c1_tile(u), mf = tt >> 2, nn = tt & 3;
-            x1[u] = tr_frag(ix, XS, 16 * mf, ln);
-            x2[u] = tr_frag(ix + B2_ROWS * XS, XS, 16 * mf, ln);
-            h1[u] = tr_frag(ih, HS, 16 * nn, ln);
-            h2[u] = tr_frag(ih + B2_ROWS * HS, HS, 16 * nn, ln);
-        }
+        for (int u = 0; u < NC1; ++u)
+            if (c1_on(u)) {
+                const int mf = c1_tile(u) >> 2;
+                x1[u] = tr_frag(ix, XS, 16 * mf, ln);
+                x2[u] = tr_frag(ix + B2_ROWS * XS, XS, 16 * mf, ln);
+            }
         const int e0 = e.X + eW - a.e_dz + ((mat || !ROOT) ? e.a : e.x);
         const int e1 = e.X + e.H;
         if (!acc_empty) {
 #pragma unroll
             for (int i = 0; i < NK0; ++i) acc0[i] = ldexp4(acc0[i], e0 - E0);
 #pragma unroll
-            for (int u = 0; u < NC1; ++u) acc1[u] = ldexp4(acc1[u], e1 - E1);
+            for (int u = 0; u < NC1; ++u)
+                if (c1_on(u)) acc1[u] = ldexp4(acc1[u], e1 - E1[u]);
         }
         E0 = e0;
-        E1 = e1;
+#pragma unroll
+        for (int u = 0; u < NC1; ++u)
+            if (c1_on(u)) E1[u] = e1;
         acc_empty = false;
 #pragma unroll
         for (int i = 0; i < NK0; ++i)
             if (c0_kt(i) < KT) acc0[i] = mfma3(a1, a2, b1[i], b2[i], acc0[i]);
 #pragma unroll
         for (int u = 0; u < NC1; ++u)
-            if (c1_tile(u) < C1_TILES) acc1[u] = mfma3(x1[u], x2[u], h1[u], h2[u], acc1[u]);
+            if (c1_on(u)) acc1[u] = mfma3(x1[u], x2[u], h1, h2, acc1[u]);
+    };
+    auto stage_c_of = [&](const L16 *buf, const Exps &e, bool hd) __attribute__((always_inline)) {
+        if (hd) stage_c(buf, e, std::true_type{});
+        else stage_c(buf, e, std::false_type{});
     };
 
     // ---- pipeline over the slice's chunks (two LDS buffers):
@@ -513,13 +574,16 @@ __global__ __launch_bounds__(B2_THREADS, 1) void k_bwd2(B2Args a) {
     //   barrier
     //   (and, before the second barrier, chunk c + 1's maxima: its loads have
     //   landed by then -- published to the next iteration's staging)
+    // The slice's j-th chunk is c = s + j S and uses buffer (and maxima
+    // slot) j & 1.  hd / hdn / hdp: chunk c / its successor / its
+    // predecessor has dy rows (uniform; once false it stays false).
     Pre pre;
-    pre.xi = XR ? iload(cb) : 0;
+    pre.xi = XR ? iload(s) : 0;
     if (XR) asm volatile("" : "+v"(pre.xi));  // (the first chunk's n_id: waited here once)
     Exps ep{0, 0, 0, 0};
-    if (cb < ce) {
-        load(cb, pre);
-        if (LAG) publish_max(pre, cb & 1);
+    if (s < C) {
+        load(s, pre);
+        if (LAG) publish_max(pre, 0, s < Cs);
     }
     if (LAG) lds_barrier();
 #ifdef NGNN_B2_SETPRIO
@@ -527,41 +591,49 @@ __global__ __launch_bounds__(B2_THREADS, 1) void k_bwd2(B2Args a) {
     // MI355X_MICROARCH.md, scheduling item 4)
     if (wv >= 4) __builtin_amdgcn_s_setprio(1);
 #endif
-    for (int c = cb; c < ce; ++c) {
-        L16 *cur = lb + (c & 1) * BUF;
+    int j = 0;
+    bool hdp = false;
+    for (int c = s; c < C; c += S, ++j) {
+        L16 *cur = lb + (j & 1) * BUF, *prv = lb + ((j & 1) ^ 1) * BUF;
+        const bool hd = c < Cs, hdn = c + S < Cs;
+        // (the buffer's dy columns 32..47 hold the values of the chunk two
+        // back, or nothing yet)
+        const bool zx = !hd && (j < 2 || c - 2 * S < Cs);
         if (LAG) {
-            // chunk c's images first (buffer c & 1: chunk c - 2's, whose
-            // stage C ran before the last two barriers), then chunk c + 1's
-            // loads, which land during stage C(c - 1) and stage B(c) -- its
-            // maxima are published after stage B
-            const Exps ec = read_exps(c & 1, ep, c == cb);
-            stage_images(pre, cur, ec);
-            load(c + 1, pre);
-            if (c > cb) stage_c(lb + ((c - 1) & 1) * BUF, ep);
+            // chunk c's images first (buffer j & 1: the chunk two back's,
+            // whose stage C ran before the last two barriers), then the next
+            // chunk's loads, which land during stage C of the previous chunk
+            // and stage B(c) -- its maxima are published after stage B
+            const Exps ec = read_exps(j & 1, ep, j == 0);
+            stage_images(pre, cur, ec, hd, zx);
+            load(c + S, pre);
+            if (j > 0) stage_c_of(prv, ep, hdp);
             lds_barrier();  // (LDS only: the next chunk's loads stay in flight)
-            stage_b(cur, ec);
-            publish_max(pre, (c + 1) & 1);
+            stage_b(cur, ec, hd);
+            publish_max(pre, (j + 1) & 1, hdn);
             lds_barrier();
             ep = ec;
+            hdp = hd;
             continue;
         }
-        if (c > cb) stage_c(lb + ((c - 1) & 1) * BUF, ep);
-        publish_max(pre, c & 1);
+        if (j > 0) stage_c_of(prv, ep, hdp);
+        publish_max(pre, j & 1, hd);
         lds_barrier();
-        const Exps ec = read_exps(c & 1, ep, c == cb);
-        stage_images(pre, cur, ec);
-        load(c + 1, pre);
+        const Exps ec = read_exps(j & 1, ep, j == 0);
+        stage_images(pre, cur, ec, hd, zx);
+        load(c + S, pre);
         lds_barrier();  // (LDS only: the next chunk's loads stay in flight)
-        stage_b(cur, ec);
+        stage_b(cur, ec, hd);
         lds_barrier();
         ep = ec;
+        hdp = hd;
     }
-    if (cb < ce) stage_c(lb + ((ce - 1) & 1) * BUF, ep);
+    if (j > 0) stage_c_of(lb + ((j - 1) & 1) * BUF, ep, hdp);
     // back to true units
 #pragma unroll
     for (int i = 0; i < NK0; ++i) acc0[i] = ldexp4(acc0[i], -E0);
 #pragma unroll
-    for (int u = 0; u < NC1; ++u) acc1[u] = ldexp4(acc1[u], -E1);
+    for (int u = 0; u < NC1; ++u) acc1[u] = ldexp4(acc1[u], -E1[u]);
 
     // ---- this workgroup's part of slab s (zeros for an empty slice)
     float *slab = a.slab + static_cast<int64_t>(s) * b2_slab_floats(K0, F1);
