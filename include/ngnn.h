@@ -639,8 +639,8 @@ int ngnn_sage_dgrad_fused(const float *dy, int64_t ldy, const float *y, int64_t 
  * bytes, 16-B aligned, ZERO-FILLED before its first use and dedicated to one
  * (Fo, K) pair: [packed W image | g], g = [n_rows][Fo rounded up to 4]
  * floats; every call leaves g zero again.  Rows >= Rn of dh are zeroed if zero_tail, else untouched.
- * NGNN_E_SHAPE when the weight image does not fit the LDS budget (callers
- * use ngnn_sage_dgrad_fused then).  Replaces autograd of lin_l + propagate
+ * NGNN_E_SHAPE when the weight image does not fit the LDS budget
+ * (ngnn_sage_dgrad_route sends no such shape here).  Replaces autograd of lin_l + propagate
  * (sage.py:34, PyG SAGEConv [ext]). */
 size_t ngnn_sage_dgrad_lowdim_workspace_bytes(int64_t n_rows, int64_t Fo, int64_t K);
 int ngnn_sage_dgrad_lowdim(const float *dy, int64_t ldy, const float *y, int64_t ldyy,
@@ -648,6 +648,23 @@ int ngnn_sage_dgrad_lowdim(const float *dy, int64_t ldy, const float *y, int64_t
                            int64_t K, const int32_t *rowptr, const int32_t *col, int64_t n_rows,
                            const int32_t *r_ptr, const int32_t *rnext_ptr, int reduce, float *dh,
                            int64_t ldd, int zero_tail, void *ws, size_t ws_bytes, void *stream);
+/* Which of the input-gradient entries above a [Fo, K] layer's backward
+ * takes (added within ABI 22) -- a pure function of its arguments, no
+ * device call; the entries' own shape checks use the same predicates:
+ *   deterministic != 0                          NGNN_DGRAD_GEMM_GATHER
+ *   else Fo < K, SUM / MEAN, and a shape ngnn_sage_dgrad_lowdim does not
+ *     answer NGNN_E_SHAPE to                    NGNN_DGRAD_LOWDIM
+ *   else Fo <= 512 and both weights fit ngnn_sage_dgrad_fused's LDS
+ *     (8 Fo K + 8 KiB <= 150 KiB)               NGNN_DGRAD_FUSED
+ *   else                                        NGNN_DGRAD_GEMM_SCATTER
+ * The two GEMM routes: the dgrad GEMM (ngnn_sage_fwd_raw with packed
+ * [W_l^T ; W_r^T]), then ngnn_sage_dgrad_scatter / _gather.  Fo or K <= 0,
+ * or a reduce outside NGNN_REDUCE_*: NGNN_E_ARG; K >= 2^31: NGNN_E_RANGE. */
+#define NGNN_DGRAD_LOWDIM 0
+#define NGNN_DGRAD_FUSED 1
+#define NGNN_DGRAD_GEMM_SCATTER 2
+#define NGNN_DGRAD_GEMM_GATHER 3
+int ngnn_sage_dgrad_route(int64_t Fo, int64_t K, int reduce, int deterministic);
 
 /* ------------------------------------------------------ seed-row loss
  * Mean cross entropy of the first B rows of logits [*, C] (row stride ld)

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "ngnn.h"
 
@@ -32,6 +33,25 @@ inline bool aligned(const void *p, size_t a) {
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 int num_cus();  // compute units of the current device (cached; ngnn_sage_rt.hip)
+
+// Runtime int -> template argument: f(std::integral_constant<int, V>{}) for
+// the first V of the list equal to v; the last V is the default, as a
+// switch ladder's `default:`.  (bools: with_const<1, 0>(flag, ...))
+template <int V, int... Rest, class F>
+inline void with_const(int v, F &&f) {
+    if constexpr (sizeof...(Rest) == 0) f(std::integral_constant<int, V>{});
+    else if (v == V) f(std::integral_constant<int, V>{});
+    else with_const<Rest...>(v, f);
+}
+
+// Raises kernel Kern's dynamic-LDS limit to `bytes`, once per instantiation
+// (so once per kernel) and process.
+template <auto Kern>
+inline void max_dynamic_lds_once(size_t bytes) {
+    static const hipError_t set = hipFuncSetAttribute(
+        reinterpret_cast<const void *>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
+    (void)set;
+}
 
 // The graph slot's contract gate (ABI 20): the slot kernel keeps, in a
 // 64-bit word, (gen << 32 | bad bits) of the last load that broke the

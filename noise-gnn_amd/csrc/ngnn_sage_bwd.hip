@@ -775,12 +775,10 @@ void dh_init_launch(const float *droot, int64_t ld_droot, int64_t n_rows, const 
     const bool vec = K % 4 == 0 && ldd % 4 == 0 && aligned(dh, 16) &&
                      (!droot || (ld_droot % 4 == 0 && aligned(droot, 16)));
     const unsigned g = static_cast<unsigned>(std::min<int64_t>(ceil_div(n_rows * K, vec ? 1024 : 256), 4096));
-    if (vec)
-        hipLaunchKernelGGL(k_dh_init<true>, dim3(std::max(g, 1u)), dim3(256), 0, st, droot, ld_droot, (int)n_rows,
-                           r_ptr, rn_ptr, (int)K, dh, ldd, zero_tail);
-    else
-        hipLaunchKernelGGL(k_dh_init<false>, dim3(std::max(g, 1u)), dim3(256), 0, st, droot, ld_droot, (int)n_rows,
-                           r_ptr, rn_ptr, (int)K, dh, ldd, zero_tail);
+    with_const<1, 0>(vec, [&](auto vec_c) {
+        hipLaunchKernelGGL(k_dh_init<decltype(vec_c)::value != 0>, dim3(std::max(g, 1u)), dim3(256), 0, st, droot,
+                           ld_droot, (int)n_rows, r_ptr, rn_ptr, (int)K, dh, ldd, zero_tail);
+    });
 }
 
 // one wave per target row d < R: scale dagg[d] once, then one 256-B atomic
@@ -1167,6 +1165,123 @@ int lpr_for(int64_t K, int vec) {
     return l;
 }
 
+// ---- the input-gradient routes' shape envelopes: one copy each, read by the
+// entry points' own checks and by ngnn_sage_dgrad_route
+constexpr size_t FD_LDS_MAX = 150 * 1024;
+constexpr size_t LOWDIM_LDS_MAX = 150 * 1024;
+
+// ngnn_sage_dgrad_fused: a dz row fits its per-wave slot (else NGNN_E_SHAPE);
+// W_r and W_l (fp32) fit its LDS next to the dz slots
+bool fused_fits(int64_t Fo) { return Fo <= FD_MAXF; }
+size_t fused_w_bytes(int64_t Fo, int64_t K) {
+    return 2 * sizeof(float) * static_cast<size_t>(Fo) * static_cast<size_t>(K);
+}
+bool fused_w_fits_lds(int64_t Fo, int64_t K) {
+    return fused_w_bytes(Fo, K) + sizeof(float) * 4 * FD_MAXF <= FD_LDS_MAX;
+}
+
+// ngnn_sage_dgrad_lowdim: column tiles per wave of the MFMA pass, and its LDS
+// (the weight image + one stage of dz | g rows)
+int lowdim_ntw(int64_t K) {
+    const int64_t half = ceil_div(ceil_div(K, 16), 2);
+    int t = 1;
+    while (t < half) t <<= 1;
+    return t;
+}
+size_t lowdim_lds_bytes(int64_t Fo, int ntw) {
+    const int64_t C4 = (Fo + 3) & ~int64_t{3};
+    return sizeof(float) * static_cast<size_t>(lowdim_img_floats(Fo, 2 * ntw) + LD_ROWS * (2 * C4 + 4));
+}
+bool lowdim_fits(int64_t Fo, int64_t K) {
+    const int ntw = lowdim_ntw(K);
+    return ntw <= 16 && lowdim_lds_bytes(Fo, ntw) <= LOWDIM_LDS_MAX;
+}
+
+// The argument checks the gather, scatter and fused entries share (all three
+// take every reduce and, for MAX, the layer input and aggregate), in the
+// order of their codes.  args_ok: the entry's own pointers and sizes; ld_ok:
+// its own leading dimensions (and shape limit).  With rows to process, MAX
+// also needs its operands: max_ptrs, ldh, ld_agg.
+int dgrad_check(int reduce, bool args_ok, int64_t K, int64_t n_rows, bool ld_ok, bool max_ptrs, int64_t ldh,
+                int64_t ld_agg) {
+    NGNN_RETURN_IF(reduce < NGNN_REDUCE_SUM || reduce > NGNN_REDUCE_MAX, NGNN_E_ARG);
+    NGNN_RETURN_IF(!args_ok || K <= 0 || n_rows < 0, NGNN_E_ARG);
+    NGNN_RETURN_IF(!ld_ok, NGNN_E_SHAPE);
+    NGNN_RETURN_IF(!fits_i32(n_rows) || !fits_i32(K), NGNN_E_RANGE);
+    if (n_rows == 0 || reduce != NGNN_REDUCE_MAX) return NGNN_OK;
+    NGNN_RETURN_IF(!max_ptrs, NGNN_E_ARG);
+    NGNN_RETURN_IF(ldh < K || ld_agg < K, NGNN_E_SHAPE);
+    return NGNN_OK;
+}
+
+// ngnn_sage_wgrad's operands after validation, as its partial-sum launches
+// take them
+struct WgradArgs {
+    hipStream_t st = nullptr;
+    bool vz = false;  // 16-B staging of dz (and its mask)
+    int vh = 0;       // h / agg staging: 0 4-B, 1 16-B, 2 bf16 h
+    int mask = 0;     // y: 0 none, 1 fp32, 2 bf16
+    const float *dy = nullptr, *y = nullptr;
+    int64_t ldy = 0, ldyy = 0;
+    float yscale = 1.0f;
+    const float *h = nullptr;
+    const float *const *h_dev = nullptr;
+    int64_t ldh = 0;
+    const int64_t *h_idx = nullptr;
+    const int64_t *const *h_idx_dev = nullptr;
+    int64_t h_rows = 0;
+    const float *agg = nullptr;
+    int64_t ld_agg = 0;
+    const int32_t *rowptr = nullptr, *r_ptr = nullptr;
+    int Fo = 0, K = 0;
+    float *ws = nullptr;
+};
+
+template <int NTW, int KTW, bool SPLIT_N>
+void launch_wgrad(const WgradArgs &a, dim3 grid) {
+    with_const<1, 0>(a.vz, [&](auto vz_c) {
+        with_const<2, 1, 0>(a.vh, [&](auto vh_c) {
+            with_const<2, 1, 0>(a.mask, [&](auto m_c) {
+                hipLaunchKernelGGL((k_wgrad_partial<NTW, KTW, SPLIT_N, decltype(vz_c)::value != 0,
+                                                    decltype(vh_c)::value, decltype(m_c)::value>),
+                                   grid, dim3(512), 0, a.st, a.dy, a.ldy, a.y, a.ldyy, a.yscale, a.h, a.h_dev,
+                                   a.ldh, a.h_idx, a.h_idx_dev, a.h_rows, a.agg, a.ld_agg, a.rowptr, a.r_ptr,
+                                   a.Fo, a.K, a.ws);
+            });
+        });
+    });
+}
+
+// the 3 x bf16 split kernel (Fo chunks of 64, 16-B staging): S slices x gy K-chunks
+void launch_wgrad_x3(const WgradArgs &a, int S, int gy) {
+    const bool hb = a.vh == 2;
+    // bf16 h with Fo >= 128: two Fo tiles per wave (half the h / agg re-reads)
+    // (NGNN_WGRAD_NFW=2, read once: two Fo tiles per wave -- half the
+    // h / agg re-reads, but the bf16-mask form spills: 429 vs 250 us on
+    // config #3's layer 0, A/B only)
+    static const int nfw_max = [] {
+        const char *e = std::getenv("NGNN_WGRAD_NFW");
+        return e ? std::max(1, std::min(2, std::atoi(e))) : 1;
+    }();
+    const int nfw = hb && a.Fo >= 128 ? nfw_max : 1;
+    const size_t lds = (static_cast<size_t>(3) * WG_BM * (WG_NC * nfw + 16) + (hb ? 1 : 3) * WG_BM * X3H +
+                        static_cast<size_t>(3) * WG_BM * X3H) * 2;
+    const int gz2 = static_cast<int>(ceil_div(a.Fo, WG_NC * nfw));
+    const dim3 grid2(static_cast<unsigned>(ceil_div(static_cast<int64_t>(S) * gy, 8) * 8 * gz2));
+    with_const<1, 0>(hb, [&](auto hb_c) {
+        with_const<2, 1, 0>(a.mask, [&](auto m_c) {
+            with_const<2, 1>(nfw, [&](auto nfw_c) {
+                constexpr auto fn = k_wgrad_x3<decltype(hb_c)::value != 0, decltype(m_c)::value,
+                                               decltype(nfw_c)::value>;
+                max_dynamic_lds_once<fn>(160 * 1024);
+                hipLaunchKernelGGL(fn, grid2, dim3(512), lds, a.st, a.dy, a.ldy, a.y, a.ldyy, a.yscale, a.h,
+                                   a.h_dev, a.ldh, a.h_idx, a.h_idx_dev, a.h_rows, a.agg, a.ld_agg, a.rowptr,
+                                   a.r_ptr, a.Fo, a.K, a.ws, S, gy, gz2);
+            });
+        });
+    });
+}
+
 }  // namespace
 }  // namespace ngnn
 
@@ -1175,40 +1290,6 @@ using namespace ngnn;
 extern "C" size_t ngnn_sage_wgrad_workspace_bytes(int64_t Fo, int64_t K) {
     if (Fo <= 0 || K <= 0) return 0;
     return sizeof(float) * S_MAX * slab_floats(Fo, K);
-}
-
-template <int NTW, int KTW, bool SPLIT_N>
-static void launch_wgrad(dim3 grid, hipStream_t st, bool vz, int vh, const float *dy, int64_t ldy,
-                         const float *y, int64_t ldyy, bool y_bf16, float yscale, const float *h,
-                         const float *const *h_dev, int64_t ldh, const int64_t *h_idx,
-                         const int64_t *const *h_idx_dev, int64_t h_rows, const float *agg,
-                         int64_t ld_agg, const int32_t *rowptr, const int32_t *r_ptr, int Fo, int K,
-                         float *ws) {
-    auto go = [&](auto vz_c, auto vh_c, auto m_c) {
-        hipLaunchKernelGGL((k_wgrad_partial<NTW, KTW, SPLIT_N, decltype(vz_c)::value,
-                                            decltype(vh_c)::value, decltype(m_c)::value>),
-                           grid, dim3(512), 0, st, dy, ldy, y, ldyy, yscale, h, h_dev, ldh, h_idx,
-                           h_idx_dev, h_rows, agg, ld_agg, rowptr, r_ptr, Fo, K, ws);
-    };
-    using T = std::true_type;
-    using F = std::false_type;
-    auto with_mask = [&](auto vz_c, auto vh_c) {
-        if (y && y_bf16) go(vz_c, vh_c, std::integral_constant<int, 2>{});
-        else if (y) go(vz_c, vh_c, std::integral_constant<int, 1>{});
-        else go(vz_c, vh_c, std::integral_constant<int, 0>{});
-    };
-    using V0 = std::integral_constant<int, 0>;
-    using V1 = std::integral_constant<int, 1>;
-    using V2 = std::integral_constant<int, 2>;
-    if (vz) {
-        if (vh == 2) with_mask(T{}, V2{});
-        else if (vh) with_mask(T{}, V1{});
-        else with_mask(T{}, V0{});
-    } else {
-        if (vh == 2) with_mask(F{}, V2{});
-        else if (vh) with_mask(F{}, V1{});
-        else with_mask(F{}, V0{});
-    }
 }
 
 extern "C" int ngnn_sage_wgrad(const float *dy, int64_t ldy, const float *y, int64_t ldyy,
@@ -1245,8 +1326,13 @@ extern "C" int ngnn_sage_wgrad(const float *dy, int64_t ldy, const float *y, int
     const int vh = h_bf16 ? 2
                           : ((K % 4 == 0) && (ldh % 4 == 0) && (ld_agg % 4 == 0) &&
                              (h_dev || aligned(h, 16)) && aligned(agg, 16));  // h_dev: 16-B aligned by contract
-    hipStream_t st = as_stream(stream);
-    float *wsf = static_cast<float *>(ws);
+    WgradArgs a;
+    a.st = as_stream(stream);
+    a.vz = vz, a.vh = vh, a.mask = !y ? 0 : (y_bf16 ? 2 : 1);
+    a.dy = dy, a.ldy = ldy, a.y = y, a.ldyy = ldyy, a.yscale = yscale;
+    a.h = h, a.h_dev = h_dev, a.ldh = ldh, a.h_idx = h_idx, a.h_idx_dev = h_idx_dev, a.h_rows = h_rows;
+    a.agg = agg, a.ld_agg = ld_agg, a.rowptr = rowptr, a.r_ptr = r_ptr;
+    a.Fo = static_cast<int>(Fo), a.K = static_cast<int>(K), a.ws = static_cast<float *>(ws);
     // slices x K-chunks x Fo-chunks ~ one workgroup per CU; the kernel uses
     // min(S, R/64) slices for the device-side row bound R
     const int64_t gy = ceil_div(K, WG_KC), gz = ceil_div(Fo, WG_NC);
@@ -1254,8 +1340,6 @@ extern "C" int ngnn_sage_wgrad(const float *dy, int64_t ldy, const float *y, int
         1, std::min<int64_t>(ceil_div(n_rows, WG_BM), std::max<int64_t>(1, S_MAX / (gy * gz)))));
     const dim3 grid(S, static_cast<unsigned>(gy), static_cast<unsigned>(gz));
     const int NT = static_cast<int>(ceil_div(std::min<int64_t>(Fo, WG_NC), 16));
-#define NGNN_WG_ARGS grid, st, vz, vh, dy, ldy, y, ldyy, y_bf16, yscale, h, h_dev, ldh, h_idx, h_idx_dev, \
-                     h_rows, agg, ld_agg, rowptr, r_ptr, (int)Fo, (int)K, wsf
     // (NGNN_WGRAD_X3=0, read once: the exact-f32 MFMA kernel for every shape -- A/B)
     static const bool x3_on = [] {
         const char *e = std::getenv("NGNN_WGRAD_X3");
@@ -1265,61 +1349,34 @@ extern "C" int ngnn_sage_wgrad(const float *dy, int64_t ldy, const float *y, int
     // 767: the X3 kernel's 16-B loads read past K into the next row, and
     // store_parts zeroes those columns)
     const bool vh_x3 = vh || (!h_bf16 && (h_dev || aligned(h, 4)) && aligned(agg, 4));
-    if (NT == 4 && vz && vh_x3 && x3_on) {
-        const bool hb = vh == 2;
-        // bf16 h with Fo >= 128: two Fo tiles per wave (half the h / agg re-reads)
-        // (NGNN_WGRAD_NFW=2, read once: two Fo tiles per wave -- half the
-        // h / agg re-reads, but the bf16-mask form spills: 429 vs 250 us on
-        // config #3's layer 0, A/B only)
-        static const int nfw_max = [] {
-            const char *e = std::getenv("NGNN_WGRAD_NFW");
-            return e ? std::max(1, std::min(2, std::atoi(e))) : 1;
-        }();
-        const int nfw = hb && Fo >= 128 ? nfw_max : 1;
-        const size_t lds = (static_cast<size_t>(3) * WG_BM * (WG_NC * nfw + 16) + (hb ? 1 : 3) * WG_BM * X3H +
-                            static_cast<size_t>(3) * WG_BM * X3H) * 2;
-        const int gz2 = static_cast<int>(ceil_div(Fo, WG_NC * nfw));
-        const dim3 grid2(static_cast<unsigned>(ceil_div(static_cast<int64_t>(S) * gy, 8) * 8 * gz2));
-        auto go = [&](auto hb_c, auto m_c) {
-            constexpr bool HBv = decltype(hb_c)::value;
-            auto fn = (HBv && nfw == 2) ? k_wgrad_x3<HBv, decltype(m_c)::value, 2>
-                                        : k_wgrad_x3<HBv, decltype(m_c)::value, 1>;
-            static bool attr[3] = {false, false, false};  // per NFW; benign race: idempotent
-            if (!attr[nfw]) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(fn),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                attr[nfw] = true;
-            }
-            hipLaunchKernelGGL(fn, grid2, dim3(512), lds, st, dy, ldy, y, ldyy, yscale, h, h_dev, ldh,
-                               h_idx, h_idx_dev, h_rows, agg, ld_agg, rowptr, r_ptr, (int)Fo, (int)K, wsf, S,
-                               static_cast<int>(gy), gz2);
-        };
-        using I0 = std::integral_constant<int, 0>;
-        using I1 = std::integral_constant<int, 1>;
-        using I2 = std::integral_constant<int, 2>;
-        auto by_mask = [&](auto hb_c) {
-            if (y && y_bf16) go(hb_c, I2{});
-            else if (y) go(hb_c, I1{});
-            else go(hb_c, I0{});
-        };
-        if (hb) by_mask(std::true_type{});
-        else by_mask(std::false_type{});
-    } else if (NT == 4) launch_wgrad<1, 8, true>(NGNN_WG_ARGS);
-    else if (NT == 1) launch_wgrad<1, 2, false>(NGNN_WG_ARGS);
-    else if (NT == 2) launch_wgrad<2, 2, false>(NGNN_WG_ARGS);
-    else launch_wgrad<3, 2, false>(NGNN_WG_ARGS);
-#undef NGNN_WG_ARGS
+    if (NT == 4 && vz && vh_x3 && x3_on) launch_wgrad_x3(a, S, static_cast<int>(gy));
+    else if (NT == 4) launch_wgrad<1, 8, true>(a, grid);
+    else if (NT == 1) launch_wgrad<1, 2, false>(a, grid);
+    else if (NT == 2) launch_wgrad<2, 2, false>(a, grid);
+    else launch_wgrad<3, 2, false>(a, grid);
     int rc = launch_status();
     if (rc) return rc;
     const int64_t total = static_cast<int64_t>(slab_floats(Fo, K));
-    hipLaunchKernelGGL(k_wgrad_reduce, dim3(ceil_div(total, 256)), dim3(256), 0, st, wsf, r_ptr, S,
-                       (int)Fo, (int)K, dwr, dwl, dbl);
+    hipLaunchKernelGGL(k_wgrad_reduce, dim3(ceil_div(total, 256)), dim3(256), 0, a.st, a.ws, r_ptr, S,
+                       a.Fo, a.K, dwr, dwl, dbl);
     return launch_status();
 }
 
 extern "C" size_t ngnn_sage_dgrad_workspace_bytes(int64_t n_rows, int64_t K, int reduce) {
     if (reduce != NGNN_REDUCE_MAX || n_rows <= 0 || K <= 0) return 0;
     return sizeof(float) * static_cast<size_t>(n_rows) * static_cast<size_t>(K);
+}
+
+extern "C" int ngnn_sage_dgrad_route(int64_t Fo, int64_t K, int reduce, int deterministic) {
+    NGNN_RETURN_IF(Fo <= 0 || K <= 0 || reduce < NGNN_REDUCE_SUM || reduce > NGNN_REDUCE_MAX, NGNN_E_ARG);
+    NGNN_RETURN_IF(!fits_i32(K), NGNN_E_RANGE);
+    if (deterministic) return NGNN_DGRAD_GEMM_GATHER;
+    if (Fo < K && reduce != NGNN_REDUCE_MAX && lowdim_fits(Fo, K)) return NGNN_DGRAD_LOWDIM;
+    // (a wave of the fused kernel re-reads the whole of W for every row: with W
+    // streamed from L2 -- the 3-layer products hidden layer, 256 x 256: 512 KiB
+    // per row -- it ran 845 us/step; wider layers take the dgrad GEMM + scatter)
+    if (fused_fits(Fo) && fused_w_fits_lds(Fo, K)) return NGNN_DGRAD_FUSED;
+    return NGNN_DGRAD_GEMM_SCATTER;
 }
 
 extern "C" int ngnn_sage_dgrad_gather(const float *dagg, int64_t ld_dagg, const float *droot,
@@ -1329,65 +1386,41 @@ extern "C" int ngnn_sage_dgrad_gather(const float *dagg, int64_t ld_dagg, const 
                                       int reduce, const float *h, int64_t ldh, const float *agg,
                                       int64_t ld_agg, float *dh, int64_t ldd, int zero_tail,
                                       void *ws, size_t ws_bytes, void *stream) {
-    NGNN_RETURN_IF(reduce < NGNN_REDUCE_SUM || reduce > NGNN_REDUCE_MAX, NGNN_E_ARG);
-    NGNN_RETURN_IF(!dagg || !droot || !rowptr || !rowptr_t || !r_ptr || !rnext_ptr || !dh, NGNN_E_ARG);
-    NGNN_RETURN_IF(K <= 0 || n_rows < 0, NGNN_E_ARG);
-    NGNN_RETURN_IF(ld_dagg < K || ld_droot < K || ldd < K, NGNN_E_SHAPE);
-    NGNN_RETURN_IF(!fits_i32(n_rows) || !fits_i32(K), NGNN_E_RANGE);
-    if (n_rows == 0) return NGNN_OK;
+    const int rc = dgrad_check(reduce,
+                               dagg && droot && rowptr && rowptr_t && r_ptr && rnext_ptr && dh, K, n_rows,
+                               ld_dagg >= K && ld_droot >= K && ldd >= K, h && agg && col, ldh, ld_agg);
+    if (rc || n_rows == 0) return rc;
     const bool is_max = reduce == NGNN_REDUCE_MAX;
-    NGNN_RETURN_IF(is_max && (!h || !agg || !col), NGNN_E_ARG);
-    NGNN_RETURN_IF(is_max && (ldh < K || ld_agg < K), NGNN_E_SHAPE);
     NGNN_RETURN_IF(is_max && (!ws || ws_bytes < ngnn_sage_dgrad_workspace_bytes(n_rows, K, reduce)),
                    NGNN_E_WORKSPACE);
     hipStream_t st = as_stream(stream);
-    const bool vec = (K % 4 == 0) && (ld_dagg % 4 == 0) && (ld_droot % 4 == 0) && (ldd % 4 == 0) &&
-                     aligned(dagg, 16) && aligned(droot, 16) && aligned(dh, 16) &&
-                     (!is_max || ((ldh % 4 == 0) && (ld_agg % 4 == 0) && aligned(h, 16) &&
-                                  aligned(agg, 16) && aligned(ws, 16)));
-    const float *src = dagg;
-    int64_t ld_src = ld_dagg;
-    auto go = [&](auto vec_c, auto lpr_c) {
-        constexpr int VECv = decltype(vec_c)::value;
-        constexpr int LPRv = decltype(lpr_c)::value;
-        const unsigned grid = static_cast<unsigned>(ceil_div(n_rows, 256 / LPRv));
-        if (is_max) {
-            float *gd = static_cast<float *>(ws);
-            hipLaunchKernelGGL((k_max_gdist<VECv, LPRv>), dim3(grid), dim3(256), 0, st, dagg,
-                               ld_dagg, rowptr, col, (int)n_rows, r_ptr, (int)K, h, ldh, agg, ld_agg,
-                               gd);
-            src = gd;
-            ld_src = K;
-            hipLaunchKernelGGL((k_dgrad_gather<VECv, LPRv, NGNN_REDUCE_MAX>), dim3(grid), dim3(256),
-                               0, st, src, ld_src, droot, ld_droot, rowptr, rowptr_t, col_t,
-                               (int)n_rows, r_ptr, rnext_ptr, (int)K, h, ldh, agg, ld_agg, dh, ldd,
-                               zero_tail);
-        } else if (reduce == NGNN_REDUCE_MEAN) {
-            hipLaunchKernelGGL((k_dgrad_gather<VECv, LPRv, NGNN_REDUCE_MEAN>), dim3(grid), dim3(256),
-                               0, st, src, ld_src, droot, ld_droot, rowptr, rowptr_t, col_t,
-                               (int)n_rows, r_ptr, rnext_ptr, (int)K, h, ldh, agg, ld_agg, dh, ldd,
-                               zero_tail);
-        } else {
-            hipLaunchKernelGGL((k_dgrad_gather<VECv, LPRv, NGNN_REDUCE_SUM>), dim3(grid), dim3(256),
-                               0, st, src, ld_src, droot, ld_droot, rowptr, rowptr_t, col_t,
-                               (int)n_rows, r_ptr, rnext_ptr, (int)K, h, ldh, agg, ld_agg, dh, ldd,
-                               zero_tail);
-        }
-    };
-    using I4 = std::integral_constant<int, 4>;
-    using I1 = std::integral_constant<int, 1>;
-    const int lpr = lpr_for(K, vec ? 4 : 1);
-    auto dispatch_lpr = [&](auto vec_c) {
-        switch (lpr) {
-            case 4: go(vec_c, std::integral_constant<int, 4>{}); break;
-            case 8: go(vec_c, std::integral_constant<int, 8>{}); break;
-            case 16: go(vec_c, std::integral_constant<int, 16>{}); break;
-            case 32: go(vec_c, std::integral_constant<int, 32>{}); break;
-            default: go(vec_c, std::integral_constant<int, 64>{}); break;
-        }
-    };
-    if (vec) dispatch_lpr(I4{});
-    else dispatch_lpr(I1{});
+    const int vec = (K % 4 == 0) && (ld_dagg % 4 == 0) && (ld_droot % 4 == 0) && (ldd % 4 == 0) &&
+                    aligned(dagg, 16) && aligned(droot, 16) && aligned(dh, 16) &&
+                    (!is_max || ((ldh % 4 == 0) && (ld_agg % 4 == 0) && aligned(h, 16) &&
+                                 aligned(agg, 16) && aligned(ws, 16))) ? 4 : 1;
+    with_const<4, 1>(vec, [&](auto vec_c) {
+        with_const<4, 8, 16, 32, 64>(lpr_for(K, vec), [&](auto lpr_c) {
+            constexpr int VECv = decltype(vec_c)::value;
+            constexpr int LPRv = decltype(lpr_c)::value;
+            const unsigned grid = static_cast<unsigned>(ceil_div(n_rows, 256 / LPRv));
+            const float *src = dagg;
+            int64_t ld_src = ld_dagg;
+            if (is_max) {
+                float *gd = static_cast<float *>(ws);
+                hipLaunchKernelGGL((k_max_gdist<VECv, LPRv>), dim3(grid), dim3(256), 0, st, dagg,
+                                   ld_dagg, rowptr, col, (int)n_rows, r_ptr, (int)K, h, ldh, agg, ld_agg,
+                                   gd);
+                src = gd;
+                ld_src = K;
+            }
+            with_const<NGNN_REDUCE_MAX, NGNN_REDUCE_MEAN, NGNN_REDUCE_SUM>(reduce, [&](auto red_c) {
+                hipLaunchKernelGGL((k_dgrad_gather<VECv, LPRv, decltype(red_c)::value>), dim3(grid),
+                                   dim3(256), 0, st, src, ld_src, droot, ld_droot, rowptr, rowptr_t, col_t,
+                                   (int)n_rows, r_ptr, rnext_ptr, (int)K, h, ldh, agg, ld_agg, dh, ldd,
+                                   zero_tail);
+            });
+        });
+    });
     return launch_status();
 }
 
@@ -1398,43 +1431,18 @@ extern "C" int ngnn_sage_dgrad_scatter(const float *dagg, int64_t ld_dagg, const
                                        const float *h, int64_t ldh, const float *agg,
                                        int64_t ld_agg, float *dh, int64_t ldd, int zero_tail,
                                        void *stream) {
-    NGNN_RETURN_IF(reduce < NGNN_REDUCE_SUM || reduce > NGNN_REDUCE_MAX, NGNN_E_ARG);
-    NGNN_RETURN_IF(!dagg || !droot || !rowptr || !r_ptr || !rnext_ptr || !dh, NGNN_E_ARG);
-    NGNN_RETURN_IF(K <= 0 || n_rows < 0, NGNN_E_ARG);
-    NGNN_RETURN_IF(ld_dagg < K || ld_droot < K || ldd < K, NGNN_E_SHAPE);
-    NGNN_RETURN_IF(!fits_i32(n_rows) || !fits_i32(K), NGNN_E_RANGE);
-    if (n_rows == 0) return NGNN_OK;
-    const bool is_max = reduce == NGNN_REDUCE_MAX;
-    NGNN_RETURN_IF(is_max && (!h || !agg), NGNN_E_ARG);
-    NGNN_RETURN_IF(is_max && (ldh < K || ld_agg < K), NGNN_E_SHAPE);
+    const int rc = dgrad_check(reduce, dagg && droot && rowptr && r_ptr && rnext_ptr && dh, K,
+                               n_rows, ld_dagg >= K && ld_droot >= K && ldd >= K, h && agg, ldh, ld_agg);
+    if (rc || n_rows == 0) return rc;
     hipStream_t st = as_stream(stream);
     dh_init_launch(droot, ld_droot, n_rows, r_ptr, rnext_ptr, K, dh, ldd, zero_tail, st);
     const unsigned g = static_cast<unsigned>(std::min<int64_t>(ceil_div(n_rows, 4), 2048));
-    if (reduce == NGNN_REDUCE_MEAN)
-        hipLaunchKernelGGL((k_dgrad_scatter<NGNN_REDUCE_MEAN>), dim3(g), dim3(256), 0, st, dagg,
+    with_const<NGNN_REDUCE_MEAN, NGNN_REDUCE_SUM, NGNN_REDUCE_MAX>(reduce, [&](auto red_c) {
+        hipLaunchKernelGGL((k_dgrad_scatter<decltype(red_c)::value>), dim3(g), dim3(256), 0, st, dagg,
                            ld_dagg, rowptr, col, (int)n_rows, r_ptr, (int)K, h, ldh, agg, ld_agg, dh,
                            ldd);
-    else if (reduce == NGNN_REDUCE_SUM)
-        hipLaunchKernelGGL((k_dgrad_scatter<NGNN_REDUCE_SUM>), dim3(g), dim3(256), 0, st, dagg,
-                           ld_dagg, rowptr, col, (int)n_rows, r_ptr, (int)K, h, ldh, agg, ld_agg, dh,
-                           ldd);
-    else
-        hipLaunchKernelGGL((k_dgrad_scatter<NGNN_REDUCE_MAX>), dim3(g), dim3(256), 0, st, dagg,
-                           ld_dagg, rowptr, col, (int)n_rows, r_ptr, (int)K, h, ldh, agg, ld_agg, dh,
-                           ldd);
+    });
     return launch_status();
-}
-
-static int dgrad_num_cus() {
-    static int n = 0;
-    if (!n) {
-        int dev = 0, v = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
-            v = 256;
-        n = v;
-    }
-    return n;
 }
 
 extern "C" int ngnn_sage_dgrad_fused(const float *dy, int64_t ldy, const float *y, int64_t ldyy,
@@ -1444,16 +1452,11 @@ extern "C" int ngnn_sage_dgrad_fused(const float *dy, int64_t ldy, const float *
                                      const int32_t *rnext_ptr, int reduce, const float *h,
                                      int64_t ldh, const float *agg, int64_t ld_agg, float *dh,
                                      int64_t ldd, int zero_tail, void *stream) {
-    NGNN_RETURN_IF(reduce < NGNN_REDUCE_SUM || reduce > NGNN_REDUCE_MAX, NGNN_E_ARG);
-    NGNN_RETURN_IF(!dy || !wl || !wr || !rowptr || !r_ptr || !rnext_ptr || !dh, NGNN_E_ARG);
-    NGNN_RETURN_IF(Fo <= 0 || K <= 0 || n_rows < 0, NGNN_E_ARG);
-    NGNN_RETURN_IF(Fo > FD_MAXF, NGNN_E_SHAPE);
-    NGNN_RETURN_IF(ldy < Fo || (y && ldyy < Fo) || ldd < K, NGNN_E_SHAPE);
-    NGNN_RETURN_IF(!fits_i32(n_rows) || !fits_i32(K), NGNN_E_RANGE);
-    if (n_rows == 0) return NGNN_OK;
-    const bool is_max = reduce == NGNN_REDUCE_MAX;
-    NGNN_RETURN_IF(is_max && (!h || !agg), NGNN_E_ARG);
-    NGNN_RETURN_IF(is_max && (ldh < K || ld_agg < K), NGNN_E_SHAPE);
+    const int rc = dgrad_check(reduce,
+                               dy && wl && wr && rowptr && r_ptr && rnext_ptr && dh && Fo > 0, K, n_rows,
+                               fused_fits(Fo) && ldy >= Fo && (!y || ldyy >= Fo) && ldd >= K, h && agg, ldh,
+                               ld_agg);
+    if (rc || n_rows == 0) return rc;
     hipStream_t st = as_stream(stream);
     dh_init_launch(nullptr, K, n_rows, r_ptr, rnext_ptr, K, dh, ldd, zero_tail, st);
     // W in LDS when both fit next to the dz slots (persistent workgroups,
@@ -1466,40 +1469,20 @@ extern "C" int ngnn_sage_dgrad_fused(const float *dy, int64_t ldy, const float *
         const char *e = std::getenv("NGNN_DGRAD_LDSW");
         return e ? std::atoi(e) : -1;
     }();
-    const size_t wbytes = 2 * sizeof(float) * static_cast<size_t>(Fo) * static_cast<size_t>(K);
-    const bool lds_w = ((Fo * K) % 4 == 0) && aligned(wl, 16) && aligned(wr, 16) &&
-                       wbytes + sizeof(float) * 4 * FD_MAXF <= 150 * 1024 &&
+    const bool lds_w = ((Fo * K) % 4 == 0) && aligned(wl, 16) && aligned(wr, 16) && fused_w_fits_lds(Fo, K) &&
                        (ldsw_env == 1 || (ldsw_env < 0 && Fo >= 32));
     const unsigned g = static_cast<unsigned>(
-        std::min<int64_t>(ceil_div(n_rows * ceil_div(K, 64), 4), lds_w ? dgrad_num_cus() : 1024));
-    auto go = [&](auto red_c, auto lds_c) {
-        constexpr int RED_ = decltype(red_c)::value;
-        constexpr bool L_ = decltype(lds_c)::value;
-        auto fn = k_dgrad_fused<RED_, L_>;
-        if (L_) {
-            static bool attr = false;
-            if (!attr) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(fn),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-                attr = true;
-            }
-        }
-        hipLaunchKernelGGL(fn, dim3(g), dim3(256), L_ ? wbytes : 0, st, dy, ldy, y, ldyy, yscale,
-                           wl, wr, (int)Fo, (int)K, rowptr, col, (int)n_rows, r_ptr, h, ldh, agg,
-                           ld_agg, dh, ldd);
-    };
-    using RM = std::integral_constant<int, NGNN_REDUCE_MEAN>;
-    using RS = std::integral_constant<int, NGNN_REDUCE_SUM>;
-    using RX = std::integral_constant<int, NGNN_REDUCE_MAX>;
-    using T = std::true_type;
-    using Fb = std::false_type;
-    if (reduce == NGNN_REDUCE_MEAN) {
-        if (lds_w) go(RM{}, T{}); else go(RM{}, Fb{});
-    } else if (reduce == NGNN_REDUCE_SUM) {
-        if (lds_w) go(RS{}, T{}); else go(RS{}, Fb{});
-    } else {
-        if (lds_w) go(RX{}, T{}); else go(RX{}, Fb{});
-    }
+        std::min<int64_t>(ceil_div(n_rows * ceil_div(K, 64), 4), lds_w ? num_cus() : 1024));
+    with_const<NGNN_REDUCE_MEAN, NGNN_REDUCE_SUM, NGNN_REDUCE_MAX>(reduce, [&](auto red_c) {
+        with_const<1, 0>(lds_w, [&](auto lds_c) {
+            constexpr bool L_ = decltype(lds_c)::value != 0;
+            constexpr auto fn = k_dgrad_fused<decltype(red_c)::value, L_>;
+            if constexpr (L_) max_dynamic_lds_once<fn>(FD_LDS_MAX);
+            hipLaunchKernelGGL(fn, dim3(g), dim3(256), L_ ? fused_w_bytes(Fo, K) : 0, st, dy, ldy, y, ldyy,
+                               yscale, wl, wr, (int)Fo, (int)K, rowptr, col, (int)n_rows, r_ptr, h, ldh, agg,
+                               ld_agg, dh, ldd);
+        });
+    });
     return launch_status();
 }
 
@@ -1510,30 +1493,16 @@ int lowdim_scatter_launch(const float *dy, int64_t ldy, const int32_t *rowptr, c
                           const int32_t *r_ptr, int Fo, int C4, float *g, int mean, hipStream_t st) {
     const int gs = static_cast<int>(std::min<int64_t>(ceil_div(n_rows, 4), 2048));
     if (gs <= 0) return NGNN_OK;
-    auto go = [&](auto mean_c) {
-        hipLaunchKernelGGL((k_lowdim_scatter<decltype(mean_c)::value, false>), dim3(gs), dim3(256), 0, st, dy, ldy,
-                           (const float *)nullptr, Fo, 1.0f, rowptr, col, n_rows, r_ptr, Fo, C4, g, gs,
+    with_const<1, 0>(mean != 0, [&](auto mean_c) {
+        hipLaunchKernelGGL((k_lowdim_scatter<decltype(mean_c)::value != 0, false>), dim3(gs), dim3(256), 0, st, dy,
+                           ldy, (const float *)nullptr, Fo, 1.0f, rowptr, col, n_rows, r_ptr, Fo, C4, g, gs,
                            (const float *)nullptr, (const float *)nullptr, int64_t{0}, 0, 0, (float *)nullptr);
-    };
-    if (mean) go(std::true_type{});
-    else go(std::false_type{});
+    });
     return launch_status();
 }
 }  // namespace ngnn
 
 // ---- low-dimensional input gradient: C ABI
-static int lowdim_ntw(int64_t K) {
-    const int64_t half = ceil_div(ceil_div(K, 16), 2);
-    int t = 1;
-    while (t < half) t <<= 1;
-    return t;
-}
-static size_t lowdim_lds_bytes(int64_t Fo, int ntw) {
-    const int64_t C4 = (Fo + 3) & ~int64_t{3};
-    return sizeof(float) * static_cast<size_t>(lowdim_img_floats(Fo, 2 * ntw) + LD_ROWS * (2 * C4 + 4));
-}
-constexpr size_t LOWDIM_LDS_MAX = 150 * 1024;
-
 extern "C" size_t ngnn_sage_dgrad_lowdim_workspace_bytes(int64_t n_rows, int64_t Fo, int64_t K) {
     if (n_rows <= 0 || Fo <= 0 || K <= 0) return 0;
     const size_t img = sizeof(float) * static_cast<size_t>(lowdim_img_floats(Fo, 2 * lowdim_ntw(K)));
@@ -1552,9 +1521,9 @@ extern "C" int ngnn_sage_dgrad_lowdim(const float *dy, int64_t ldy, const float 
     NGNN_RETURN_IF(Fo <= 0 || K <= 0 || n_rows < 0, NGNN_E_ARG);
     NGNN_RETURN_IF(ldy < Fo || (y && ldyy < Fo) || ldd < K || ldw < K, NGNN_E_SHAPE);
     NGNN_RETURN_IF(!fits_i32(n_rows) || !fits_i32(K), NGNN_E_RANGE);
-    const int ntw = lowdim_ntw(K);
-    NGNN_RETURN_IF(ntw > 16 || lowdim_lds_bytes(Fo, ntw) > LOWDIM_LDS_MAX, NGNN_E_SHAPE);
+    NGNN_RETURN_IF(!lowdim_fits(Fo, K), NGNN_E_SHAPE);
     if (n_rows == 0) return NGNN_OK;
+    const int ntw = lowdim_ntw(K);
     NGNN_RETURN_IF(!ws || ws_bytes < ngnn_sage_dgrad_lowdim_workspace_bytes(n_rows, Fo, K) ||
                        !aligned(ws, 16), NGNN_E_WORKSPACE);
     hipStream_t st = as_stream(stream);
@@ -1568,42 +1537,26 @@ extern "C" int ngnn_sage_dgrad_lowdim(const float *dy, int64_t ldy, const float 
     }
     const int gs = static_cast<int>(std::min<int64_t>(ceil_div(n_rows, 4), 2048));
     const int gp = static_cast<int>(ceil_div(img_n, 256));
-    auto scatter = [&](auto mean_c, auto mask_c) {
-        hipLaunchKernelGGL((k_lowdim_scatter<decltype(mean_c)::value, decltype(mask_c)::value>),
-                           dim3(gs + gp), dim3(256), 0, st, dy, ldy, y, ldyy, yscale, rowptr, col,
-                           (int)n_rows, r_ptr, (int)Fo, C4, g, gs, wl, wr, ldw, (int)K, ntp, img);
-    };
-    using T = std::true_type;
-    using Fb = std::false_type;
-    const bool mean = reduce == NGNN_REDUCE_MEAN;
-    if (mean) { if (y) scatter(T{}, T{}); else scatter(T{}, Fb{}); }
-    else { if (y) scatter(Fb{}, T{}); else scatter(Fb{}, Fb{}); }
+    with_const<1, 0>(reduce == NGNN_REDUCE_MEAN, [&](auto mean_c) {
+        with_const<1, 0>(y != nullptr, [&](auto mask_c) {
+            hipLaunchKernelGGL((k_lowdim_scatter<decltype(mean_c)::value != 0, decltype(mask_c)::value != 0>),
+                               dim3(gs + gp), dim3(256), 0, st, dy, ldy, y, ldyy, yscale, rowptr, col,
+                               (int)n_rows, r_ptr, (int)Fo, C4, g, gs, wl, wr, ldw, (int)K, ntp, img);
+        });
+    });
     int rc = launch_status();
     if (rc) return rc;
     const bool vout = (K % 4 == 0) && (ldd % 4 == 0) && aligned(dh, 16);
     const size_t lds = lowdim_lds_bytes(Fo, ntw);
     const unsigned gg = static_cast<unsigned>(
-        std::max<int64_t>(1, std::min<int64_t>(dgrad_num_cus(), ceil_div(n_rows, 16))));
-    auto gemm = [&](auto ntw_c, auto vout_c) {
-        auto fn = k_lowdim_gemm<decltype(ntw_c)::value, decltype(vout_c)::value>;
-        static bool attr = false;
-        if (!attr) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(fn),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, LOWDIM_LDS_MAX);
-            attr = true;
-        }
-        hipLaunchKernelGGL(fn, dim3(gg), dim3(512), lds, st, dy, ldy, y, ldyy, yscale, img,
-                           (int)Fo, (int)K, (int)n_rows, r_ptr, rnext_ptr, g, C4, dh, ldd);
-    };
-    auto by_ntw = [&](auto vout_c) {
-        switch (ntw) {
-            case 1: gemm(std::integral_constant<int, 1>{}, vout_c); break;
-            case 2: gemm(std::integral_constant<int, 2>{}, vout_c); break;
-            case 4: gemm(std::integral_constant<int, 4>{}, vout_c); break;
-            case 8: gemm(std::integral_constant<int, 8>{}, vout_c); break;
-            default: gemm(std::integral_constant<int, 16>{}, vout_c); break;
-        }
-    };
-    if (vout) by_ntw(T{}); else by_ntw(Fb{});
+        std::max<int64_t>(1, std::min<int64_t>(num_cus(), ceil_div(n_rows, 16))));
+    with_const<1, 0>(vout, [&](auto vout_c) {
+        with_const<1, 2, 4, 8, 16>(ntw, [&](auto ntw_c) {
+            constexpr auto fn = k_lowdim_gemm<decltype(ntw_c)::value, decltype(vout_c)::value != 0>;
+            max_dynamic_lds_once<fn>(LOWDIM_LDS_MAX);
+            hipLaunchKernelGGL(fn, dim3(gg), dim3(512), lds, st, dy, ldy, y, ldyy, yscale, img,
+                               (int)Fo, (int)K, (int)n_rows, r_ptr, rnext_ptr, g, C4, dh, ldd);
+        });
+    });
     return launch_status();
 }

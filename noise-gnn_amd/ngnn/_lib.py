@@ -30,6 +30,8 @@ WL_PREPACKED = 0x1000   # same: ws already holds ngnn_pack_weight(wl)
 OUT_BF16 = 0x2000   # same: out rows bf16 (a bf16 model's hidden activations)
 SAGE2_PREP, SAGE2_EDGE, SAGE2_MAIN, SAGE2_NARROW, SAGE2_ALL = 1, 2, 4, 8, 15  # ngnn_sage2_fwd stages
 F32, BF16 = 0, 1
+# ngnn_sage_dgrad_route's answers (include/ngnn.h NGNN_DGRAD_*)
+DGRAD_LOWDIM, DGRAD_FUSED, DGRAD_GEMM_SCATTER, DGRAD_GEMM_GATHER = 0, 1, 2, 3
 NOISE_SIGN = 1  # ngnn_node_noise_fwd / _bwd's flags (include/ngnn.h NGNN_NOISE_SIGN)
 
 # name -> (restype, argtypes); mirrors include/ngnn.h one to one
@@ -117,6 +119,7 @@ SIGNATURES = {
     "ngnn_sage_dgrad_lowdim": (_int, [_p, _i64, _p, _i64, ctypes.c_float, _p, _p, _i64, _i64,
                                       _i64, _p, _p, _i64, _p, _p, _int, _p, _i64, _int, _p, _sz,
                                       _p]),
+    "ngnn_sage_dgrad_route": (_int, [_i64, _i64, _int, _int]),
     # (added within ABI 22: SAGEPL's per-node input noise)
     "ngnn_node_noise_fwd": (_int, [_p, _i64, _p, _i64, _i64, _p, _i64, _i64, ctypes.c_float, _int, _p,
                                    _i64, _p, _p]),

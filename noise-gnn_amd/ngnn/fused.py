@@ -416,15 +416,6 @@ def const_bounds(dev, L: int, R: int) -> torch.Tensor:
     return bnd
 
 
-def _dgrad_fused_ok(Fo: int, K: int) -> bool:
-    """ngnn_sage_dgrad_fused (per target row, VALU products, W_r and W_l in
-    LDS) only while both weights fit its LDS: a wave re-reads the whole of W
-    for every row, so with W streamed from L2 (the 3-layer products hidden
-    layer, 256 x 256: 512 KiB per row) it ran 845 us/step.  Wider layers take
-    the dgrad GEMM (MFMA, rows < R) + scatter."""
-    return Fo <= 512 and 2 * Fo * K * 4 + 4 * 512 * 4 <= 150 * 1024
-
-
 # the two-layer weight-stationary forward (ngnn_sage2_fwd) for the shapes it
 # covers; False: always the per-layer kernels (A/B switch, tests)
 _use_fwd2 = True
@@ -761,6 +752,190 @@ def sage2_backward(dy, block: Block, reduce: str, acts, agg0, params, p_drop: fl
     return grads
 
 
+def _bwd_bounds(ctx, dout, L: int, need_dx: bool):
+    """The stack backward's device-side row bounds: (bnd, bp, pre_top,
+    rows_hint).
+    bnd: the int32 tensor that holds them.  The launches take raw addresses
+    into it, so the caller must keep it referenced until its last launch is
+    enqueued (a dropped bnd is reused by the next allocation).
+    bp: bp[L] addresses the rows of dout that can be nonzero, bp[i] the same
+    for d(acts[i]) (prefix_stats takes max(bnd[i], R, ...), so R is a valid
+    initial bnd[i]).
+    rows_hint: the top bound on the host, when the loss told us.
+    pre_top: bp[L - 1] is the producer's precomputed bound (graph slot), no
+    prefix-stats launch for the top layer."""
+    block, dev = ctx.block, dout.device
+    rows_hint = getattr(dout, "_ngnn_nonzero_rows", None)  # set by ngnn.losses
+    pre_top = (L > 0 and block.r_next is not None and rows_hint is not None
+               and int(rows_hint) == block.r_next[1])
+    # bound entries some launch writes: row_extent (bnd[L]) without a hint,
+    # prefix stats for layers L-1 .. 1 (and 0 when dx is needed)
+    written = rows_hint is None or any(
+        not (pre_top and i == L - 1) for i in range(L - 1, -1 if need_dx else 0, -1))
+    if written:
+        # a fresh copy of the cached constant (a device-to-device memcpy:
+        # no fill kernel in the step)
+        bnd = torch.empty(L + 1, dtype=torch.int32, device=dev)
+        bnd.copy_(const_bounds(dev, L, int(rows_hint) if rows_hint is not None else 0))
+    else:  # read-only: a cached constant (no fill launch per step)
+        bnd = const_bounds(dev, L, int(rows_hint))
+    bp = [bnd.data_ptr() + 4 * j for j in range(L + 1)]
+    if ctx.h_partial and not pre_top:
+        # the forward wrote h only below the slot's R' (sage2_forward)
+        raise _lib.NGNNError("this backward needs hidden rows past the slot's bound: the loss "
+                             "must read rows < the slot's batch size (seed_cross_entropy)")
+    if pre_top:
+        bp[L - 1] = block.r_next[0].data_ptr()
+    return bnd, bp, pre_top, rows_hint
+
+
+def _layer_wgrad(lib, stream, block: Block, i: int, dy, ymask, yscale: float, h_in, agg, wl, bl, wr,
+                 gcn: bool, views, seed_rows, red: int, r_ptr: int):
+    """One layer's weight gradients over rows < *r_ptr: (agg, dwl, dbl, dwr).
+    agg None (a narrow-mode layer): the K-wide aggregate the kernel reads is
+    gathered first -- seed_rows rows when the loss told us R (the seed rows),
+    else every row -- and returned for the input gradient."""
+    dev, N = dy.device, block.n_dst
+    Fo, K = wl.shape
+    # gradient buffers: the data-parallel bucket's views when the caller
+    # registered them (a fresh view each time, so autograd adopts it as
+    # .grad instead of copying it), else new tensors
+    dwl, dbl, dwr = ((g.view(q.shape) if g is not None else torch.empty_like(q))
+                     for g, q in zip(views, (wl, bl, wr)))
+    if gcn:
+        dwr = _workspace(dev, "gcn_dwr", wr.numel() * 4).view(torch.float32)[:wr.numel()].view(wr.shape)
+    if agg is None:
+        if i == 0 and block.x_dev is not None:  # (zero_copy_ok excludes it)
+            raise _lib.NGNNError("layer-0 aggregate rebuild from a zero-copy input")
+        R = N if seed_rows is None else int(seed_rows)
+        agg = torch.empty(max(R, 1), K, dtype=torch.float32, device=dev)
+        with _timing.span("sage_agg_seed_rows", 0, 0):
+            _lib.check(lib.ngnn_seg_agg_fwd(
+                _lib.ptr(h_in), h_in.stride(0), K, _lib.ptr(block.rowptr), _lib.ptr(block.col), R, red,
+                _lib.BF16 if h_in.dtype == torch.bfloat16 else _lib.F32, _lib.ptr(agg), agg.stride(0),
+                stream), "ngnn_seg_agg_fwd")
+    y_bf16 = ymask is not None and ymask.dtype == torch.bfloat16
+    ws = _workspace(dev, "wgrad", lib.ngnn_sage_wgrad_workspace_bytes(Fo, K))
+    with _timing.span("sage_wgrad", 0, 0):  # row bound is device-side: no host count
+        rc = lib.ngnn_sage_wgrad(
+            _lib.ptr(dy), dy.stride(0), _lib.ptr(ymask), ymask.stride(0) if ymask is not None else Fo,
+            yscale, _lib.ptr(h_in), _lib.ptr(block.x_dev) if i == 0 else None, None,
+            _lib.ptr(block.xrow_dev) if i == 0 else None, block.x_rows if i == 0 else 0,
+            int(h_in.dtype == torch.bfloat16) | (2 if y_bf16 else 0), h_in.stride(0), _lib.ptr(agg),
+            agg.stride(0), _lib.ptr(block.rowptr), N, r_ptr, Fo, K, _lib.ptr(dwl), _lib.ptr(dbl),
+            _lib.ptr(dwr), _lib.ptr(ws), ws.numel(), stream)
+    _lib.check(rc, "ngnn_sage_wgrad")
+    return agg, dwl, dbl, dwr
+
+
+# The four input-gradient launchers, one per route of ngnn_sage_dgrad_route.
+# Each returns dh [N, K] = d(layer input) for rows < *rn_ptr from dy rows <
+# *r_ptr (ymask / yscale: the ReLU + dropout backward of a hidden layer).
+
+def _dgrad_lowdim(lib, stream, block: Block, dy, ymask, yscale, wl, wr, red, h_in, agg, r_ptr, rn_ptr,
+                  zero_tail):
+    # narrow-space path: scatter dz (Fo wide), then one MFMA pass
+    dev, N = dy.device, block.n_dst
+    Fo, K = wl.shape
+    dh = torch.empty(N, K, dtype=torch.float32, device=dev)
+    wlc, wrc = wl.detach().contiguous(), wr.detach().contiguous()
+    gws = _workspace(dev, ("dgrad_lowdim", Fo, K),  # g stays zero per shape
+                     lib.ngnn_sage_dgrad_lowdim_workspace_bytes(N, Fo, K), zero=True)
+    with _timing.span("sage_dgrad_lowdim", 0, 0):
+        rc = lib.ngnn_sage_dgrad_lowdim(
+            _lib.ptr(dy), dy.stride(0), _lib.ptr(ymask), ymask.stride(0) if ymask is not None else Fo,
+            yscale, _lib.ptr(wlc), _lib.ptr(wrc), wlc.stride(0), Fo, K, _lib.ptr(block.rowptr),
+            _lib.ptr(block.col), N, r_ptr, rn_ptr, red, _lib.ptr(dh), dh.stride(0), zero_tail,
+            _lib.ptr(gws), gws.numel(), stream)
+    _lib.check(rc, "ngnn_sage_dgrad_lowdim")
+    return dh
+
+
+def _dgrad_fused(lib, stream, block: Block, dy, ymask, yscale, wl, wr, red, h_in, agg, r_ptr, rn_ptr,
+                 zero_tail):
+    # atomic path: per-row VALU products + scatter, no dgrad GEMM launch
+    N = block.n_dst
+    Fo, K = wl.shape
+    dh = torch.empty(N, K, dtype=torch.float32, device=dy.device)
+    wlc, wrc = wl.detach().contiguous(), wr.detach().contiguous()
+    with _timing.span("sage_dgrad_fused", 0, 0):
+        rc = lib.ngnn_sage_dgrad_fused(
+            _lib.ptr(dy), dy.stride(0), _lib.ptr(ymask), ymask.stride(0) if ymask is not None else Fo,
+            yscale, _lib.ptr(wlc), _lib.ptr(wrc), Fo, K, _lib.ptr(block.rowptr), _lib.ptr(block.col), N,
+            r_ptr, rn_ptr, red, _lib.ptr(h_in), h_in.stride(0), _lib.ptr(agg), agg.stride(0),
+            _lib.ptr(dh), dh.stride(0), zero_tail, stream)
+    _lib.check(rc, "ngnn_sage_dgrad_fused")
+    return dh
+
+
+def _dgrad_gemm(block: Block, dy, ymask, yscale, wl, wr, r_ptr):
+    """The GEMM routes' first launch: dg [N, 2K] = [dz W_l | dz W_r] on rows <
+    *r_ptr (ReLU/dropout backward in the staging)."""
+    N = block.n_dst
+    Fo, K = wl.shape
+    pk = pack_dgrad_weight(wl, wr)
+    dg = torch.empty(N, 2 * K, dtype=torch.float32, device=dy.device)
+    with _timing.span("sage_dgrad", 0, 0):
+        _gemm_layer(dy, Fo, N, None, "mean", None, pk, None, 2 * K, dg, False, 0.0, 0,
+                    n_rows_dev=r_ptr, xmask=ymask, xscale=yscale)
+    return dg
+
+
+def _dgrad_gemm_scatter(lib, stream, block: Block, dy, ymask, yscale, wl, wr, red, h_in, agg, r_ptr,
+                        rn_ptr, zero_tail):
+    # float atomics (as the reference's CUDA index_add_)
+    N, K = block.n_dst, wl.shape[1]
+    dg = _dgrad_gemm(block, dy, ymask, yscale, wl, wr, r_ptr)
+    dh = torch.empty(N, K, dtype=torch.float32, device=dy.device)
+    with _timing.span("sage_dgrad_scatter", 0, 0):
+        rc = lib.ngnn_sage_dgrad_scatter(
+            _lib.ptr(dg), 2 * K, _lib.ptr(dg) + 4 * K, 2 * K, _lib.ptr(block.rowptr), _lib.ptr(block.col),
+            N, r_ptr, rn_ptr, K, red, _lib.ptr(h_in), h_in.stride(0), _lib.ptr(agg), agg.stride(0),
+            _lib.ptr(dh), dh.stride(0), zero_tail, stream)
+    _lib.check(rc, "ngnn_sage_dgrad_scatter")
+    return dh
+
+
+def _dgrad_gemm_gather(lib, stream, block: Block, dy, ymask, yscale, wl, wr, red, h_in, agg, r_ptr,
+                       rn_ptr, zero_tail):
+    # the source-grouped CSR gather: fixed summation order (deterministic mode)
+    N, K = block.n_dst, wl.shape[1]
+    t = block.transposed()
+    dg = _dgrad_gemm(block, dy, ymask, yscale, wl, wr, r_ptr)
+    dh = torch.empty(N, K, dtype=torch.float32, device=dy.device)
+    gws = _workspace(dy.device, "dgrad", lib.ngnn_sage_dgrad_workspace_bytes(N, K, red))
+    with _timing.span("sage_dgrad_gather", 0, 0):
+        rc = lib.ngnn_sage_dgrad_gather(
+            _lib.ptr(dg), 2 * K, _lib.ptr(dg) + 4 * K, 2 * K, _lib.ptr(block.rowptr), _lib.ptr(block.col),
+            _lib.ptr(t.rowptr), _lib.ptr(t.col), N, r_ptr, rn_ptr, K, red, _lib.ptr(h_in),
+            h_in.stride(0), _lib.ptr(agg), agg.stride(0), _lib.ptr(dh), dh.stride(0), zero_tail,
+            _lib.ptr(gws), gws.numel(), stream)
+    _lib.check(rc, "ngnn_sage_dgrad_gather")
+    return dh
+
+
+# indexed by ngnn_sage_dgrad_route's answer (_lib.DGRAD_*)
+_DGRAD = (_dgrad_lowdim, _dgrad_fused, _dgrad_gemm_scatter, _dgrad_gemm_gather)
+_dgrad_routes: dict = {}
+
+
+def _layer_dgrad(lib, stream, block: Block, dy, ymask, yscale, wl, wr, red, deterministic, h_in, agg,
+                 r_ptr, rn_ptr, zero_tail):
+    """One layer's input gradient on the route ngnn_sage_dgrad_route names for
+    (Fo, K, reduce, deterministic) -- the one copy of the rule is the
+    library's (a pure function of the key: asked once, the eager step is
+    host-bound)."""
+    key = (wl.shape[0], wl.shape[1], red, deterministic)
+    route = _dgrad_routes.get(key)
+    if route is None:
+        route = int(lib.ngnn_sage_dgrad_route(key[0], key[1], red, int(deterministic)))
+        if route < 0:
+            _lib.check(route, "ngnn_sage_dgrad_route")
+        _dgrad_routes[key] = route
+    return _DGRAD[route](lib, stream, block, dy, ymask, yscale, wl, wr, red, h_in, agg, r_ptr, rn_ptr,
+                         zero_tail)
+
+
 class _SAGEStack(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, block: Block, reduce: str, p_drop: float, seed: int, seed_dev, gouts,
@@ -843,63 +1018,39 @@ class _SAGEStack(torch.autograd.Function):
         if gv is not None:
             gv.live = False
         dy = dout if dout.stride(1) == 1 else dout.contiguous()
-        # bnd[L] = rows of dout that can be nonzero; bnd[i] = same for d(acts[i])
-        # (prefix_stats takes max(bnd[i], R, ...), so R is a valid initial bnd[i])
-        rows_hint = getattr(dout, "_ngnn_nonzero_rows", None)  # set by ngnn.losses
-        # the producer's precomputed top-layer bound (graph slot): no prefix-stats launch
-        pre_top = (L > 0 and block.r_next is not None and rows_hint is not None
-                   and int(rows_hint) == block.r_next[1])
-        # bound entries some launch below writes: row_extent (bnd[L]) without a
-        # hint, prefix stats for layers L-1 .. 1 (and 0 when dx is needed)
-        written = rows_hint is None or any(
-            not (pre_top and i == L - 1) for i in range(L - 1, -1 if need_dx else 0, -1))
-        if written:
-            # a fresh copy of the cached constant (a device-to-device memcpy:
-            # no fill kernel in the step)
-            bnd = torch.empty(L + 1, dtype=torch.int32, device=dev)
-            bnd.copy_(const_bounds(dev, L, int(rows_hint) if rows_hint is not None else 0))
-        else:  # read-only: a cached constant (no fill launch per step)
-            bnd = const_bounds(dev, L, int(rows_hint))
-        bp = [bnd.data_ptr() + 4 * j for j in range(L + 1)]
-        if ctx.h_partial and not pre_top:
-            # the forward wrote h only below the slot's R' (sage2_forward)
-            raise _lib.NGNNError("this backward needs hidden rows past the slot's bound: the loss "
-                                 "must read rows < the slot's batch size (seed_cross_entropy)")
-        if pre_top:
-            bp[L - 1] = block.r_next[0].data_ptr()
-        bptr = lambda j: bp[j]  # noqa: E731
-        if (ctx.sage2 and pre_top and not need_dx and _use_bwd2
-                and not torch.are_deterministic_algorithms_enabled()):
-            # (a loss head's gradient arrives with its scatter done: g_pre)
-            return (None, None, None, None, None, None, None, None, None,
-                    *_absent_none(params, sage2_backward(dy, block, reduce, acts, aggs[0], sage2_params(params),
-                                                         p, bptr(2), bptr(1), views,
-                                                         g_pre=getattr(dout, "_ngnn_g_pre", None),
-                                                         root_free=params[2] is None)))
-        if (ctx.sage2 and not ctx.h_partial and not need_dx and _use_bwd2
-                and not torch.are_deterministic_algorithms_enabled()):
-            # an eager step (the reference loop after the Option-B swap: no
-            # graph slot, F.cross_entropy on out[:batch_size]): the same
-            # two-layer backward, its row bounds from dout on the device --
-            # R = the rows of dout that can be nonzero, R' their sources'
-            # bound -- instead of the per-layer kernels (which rebuilt layer
-            # 1's aggregate over every row without a loss hint)
-            if rows_hint is None:
-                _lib.check(lib.ngnn_row_extent(_lib.ptr(dy), dy.stride(0), N, dy.size(1), bptr(L),
-                                               stream), "ngnn_row_extent")
-            _lib.check(lib.ngnn_block_prefix_stats(_lib.ptr(block.rowptr), _lib.ptr(block.col),
-                                                   bptr(L), None, bptr(L - 1), block.E, stream),
-                       "ngnn_block_prefix_stats")
-            return (None, None, None, None, None, None, None, None, None,
-                    *_absent_none(params, sage2_backward(dy, block, reduce, acts, aggs[0], sage2_params(params),
-                                                         p, bptr(2), bptr(1), views, root_free=params[2] is None)))
-        if rows_hint is None:
-            _lib.check(lib.ngnn_row_extent(_lib.ptr(dy), dy.stride(0), N, dy.size(1), bptr(L),
-                                           stream), "ngnn_row_extent")
+        # bnd is never read here but must stay referenced until this function
+        # returns: every launch below reads raw addresses into it (bp), and a
+        # freed bnd is handed to the next torch.empty -- the kernels would then
+        # read overwritten row bounds (an illegal access)
+        bnd, bp, pre_top, rows_hint = _bwd_bounds(ctx, dout, L, need_dx)
         # input-gradient scatter: float atomics by default (as the reference's CUDA
         # index_add_); the source-grouped CSR gather when determinism is requested
         deterministic = torch.are_deterministic_algorithms_enabled()
-        t = block.transposed() if (deterministic and (L > 1 or need_dx)) else None
+        if ctx.sage2 and not need_dx and _use_bwd2 and not deterministic:
+            # the two-layer backward (h_partial implies pre_top here: _bwd_bounds)
+            g_pre = None
+            if pre_top:  # graph slot (a loss head's gradient arrives with its scatter done)
+                g_pre = getattr(dout, "_ngnn_g_pre", None)
+            else:
+                # an eager step (the reference loop after the Option-B swap: no
+                # graph slot, F.cross_entropy on out[:batch_size]): its row
+                # bounds from dout on the device -- R = the rows of dout that
+                # can be nonzero, R' their sources' bound -- instead of the
+                # per-layer kernels (which rebuilt layer 1's aggregate over
+                # every row without a loss hint)
+                if rows_hint is None:
+                    _lib.check(lib.ngnn_row_extent(_lib.ptr(dy), dy.stride(0), N, dy.size(1), bp[L],
+                                                   stream), "ngnn_row_extent")
+                _lib.check(lib.ngnn_block_prefix_stats(_lib.ptr(block.rowptr), _lib.ptr(block.col),
+                                                       bp[L], None, bp[L - 1], block.E, stream),
+                           "ngnn_block_prefix_stats")
+            return (None, None, None, None, None, None, None, None, None,
+                    *_absent_none(params, sage2_backward(dy, block, reduce, acts, aggs[0], sage2_params(params),
+                                                         p, bp[2], bp[1], views, g_pre,
+                                                         params[2] is None)))
+        if rows_hint is None:
+            _lib.check(lib.ngnn_row_extent(_lib.ptr(dy), dy.stride(0), N, dy.size(1), bp[L],
+                                           stream), "ngnn_row_extent")
         red = _lib.REDUCE[reduce]
         for i in reversed(range(L)):
             h_in, y_out, agg = acts[i], acts[i + 1], aggs[i]
@@ -911,121 +1062,30 @@ class _SAGEStack(torch.autograd.Function):
             gcn = wr is None  # GCN layer: SAGE with W_r = 0 (no root-term gradient)
             if gcn:
                 wr = _zeros_like_cached(wl)
-            Fo, K = wl.shape
             hidden = i != L - 1
             ymask = y_out if hidden else None
-            y_bf16 = ymask is not None and ymask.dtype == torch.bfloat16
             yscale = dropout_scale(p) if (hidden and p > 0.0) else 1.0
-            # gradient buffers: the data-parallel bucket's views when the caller
-            # registered them (a fresh view each time, so autograd adopts it as
-            # .grad instead of copying it), else new tensors
-            dwl, dbl, dwr = (
-                (g.view(q.shape) if g is not None else torch.empty_like(q))
-                for g, q in zip(views[3 * i:3 * i + 3], (wl, bl, wr)))
-            if gcn:
-                dwr = _workspace(dev, "gcn_dwr", wr.numel() * 4).view(torch.float32)[
-                    :wr.numel()].view(wr.shape)
-            if agg is None:
-                if i == 0 and block.x_dev is not None:  # (zero_copy_ok excludes it)
-                    raise _lib.NGNNError("layer-0 aggregate rebuild from a zero-copy input")
-                # narrow-mode layer: the K-wide aggregate the weight gradient
-                # reads (rows < R) gathered now -- R rows when the loss told us
-                # R (the seed rows), else every row
-                R = int(rows_hint) if (rows_hint is not None and i == L - 1) else N
-                agg = torch.empty(max(R, 1), K, dtype=torch.float32, device=dev)
-                with _timing.span("sage_agg_seed_rows", 0, 0):
-                    _lib.check(lib.ngnn_seg_agg_fwd(
-                        _lib.ptr(h_in), h_in.stride(0), K, _lib.ptr(block.rowptr),
-                        _lib.ptr(block.col), R, red,
-                        _lib.BF16 if h_in.dtype == torch.bfloat16 else _lib.F32, _lib.ptr(agg),
-                        agg.stride(0), stream), "ngnn_seg_agg_fwd")
-            wsb = lib.ngnn_sage_wgrad_workspace_bytes(Fo, K)
-            ws = _workspace(dev, "wgrad", wsb)
-            with _timing.span("sage_wgrad", 0, 0):  # row bound is device-side: no host count
-                rc = lib.ngnn_sage_wgrad(
-                    _lib.ptr(dy), dy.stride(0), _lib.ptr(ymask),
-                    ymask.stride(0) if ymask is not None else Fo, yscale, _lib.ptr(h_in),
-                    _lib.ptr(block.x_dev) if i == 0 else None,
-                    None, _lib.ptr(block.xrow_dev) if i == 0 else None,
-                    block.x_rows if i == 0 else 0,
-                    int(h_in.dtype == torch.bfloat16) | (2 if y_bf16 else 0), h_in.stride(0),
-                    _lib.ptr(agg), agg.stride(0), _lib.ptr(block.rowptr), N,
-                    bptr(i + 1), Fo, K, _lib.ptr(dwl), _lib.ptr(dbl), _lib.ptr(dwr),
-                    _lib.ptr(ws), ws.numel(), stream)
-            _lib.check(rc, "ngnn_sage_wgrad")
+            agg, dwl, dbl, dwr = _layer_wgrad(lib, stream, block, i, dy, ymask, yscale, h_in, agg, wl, bl,
+                                              wr, gcn, views[3 * i:3 * i + 3],
+                                              None if hidden else rows_hint, red, bp[i + 1])
             grads[3 * i:3 * i + 3] = [dwl, dbl, None if gcn else dwr]
             if i == 0 and not need_dx:
                 break
             if not (pre_top and i == L - 1):
                 _lib.check(lib.ngnn_block_prefix_stats(_lib.ptr(block.rowptr), _lib.ptr(block.col),
-                                                       bptr(i + 1), None, bptr(i), block.E, stream),
+                                                       bp[i + 1], None, bp[i], block.E, stream),
                            "ngnn_block_prefix_stats")
-            if y_bf16:
+            if ymask is not None and ymask.dtype == torch.bfloat16:
                 # the input-gradient kernels read an fp32 mask: widen its rows
                 # below the output-gradient bound (device-side)
+                Fo = wl.shape[0]
                 ym = _workspace(dev, "ymask_f32", N * Fo * 4).view(torch.float32)[:N * Fo].view(N, Fo)
                 _lib.check(lib.ngnn_widen_bf16_rows(_lib.ptr(ymask), ymask.stride(0), Fo, N,
-                                                    bptr(i + 1), _lib.ptr(ym), Fo, stream),
+                                                    bp[i + 1], _lib.ptr(ym), Fo, stream),
                            "ngnn_widen_bf16_rows")
                 ymask = ym
-            if not deterministic and Fo < K and reduce in ("sum", "mean"):
-                # narrow-space path: scatter dz (Fo wide), then one MFMA pass
-                dh = torch.empty(N, K, dtype=torch.float32, device=dev)
-                wlc, wrc = wl.detach().contiguous(), wr.detach().contiguous()
-                gws = _workspace(dev, ("dgrad_lowdim", Fo, K),  # g stays zero per shape
-                                 lib.ngnn_sage_dgrad_lowdim_workspace_bytes(N, Fo, K), zero=True)
-                with _timing.span("sage_dgrad_lowdim", 0, 0):
-                    rc = lib.ngnn_sage_dgrad_lowdim(
-                        _lib.ptr(dy), dy.stride(0), _lib.ptr(ymask),
-                        ymask.stride(0) if ymask is not None else Fo, yscale, _lib.ptr(wlc),
-                        _lib.ptr(wrc), wlc.stride(0), Fo, K, _lib.ptr(block.rowptr),
-                        _lib.ptr(block.col), N, bptr(i + 1), bptr(i), red, _lib.ptr(dh),
-                        dh.stride(0), int(i == 0), _lib.ptr(gws), gws.numel(), stream)
-                if rc == _lib.OK:
-                    dy = dh
-                    continue
-                if rc != _lib.E_SHAPE:
-                    _lib.check(rc, "ngnn_sage_dgrad_lowdim")
-            if not deterministic and _dgrad_fused_ok(Fo, K):
-                # atomic path: per-row VALU products + scatter, no dgrad GEMM launch
-                dh = torch.empty(N, K, dtype=torch.float32, device=dev)
-                wlc, wrc = wl.detach().contiguous(), wr.detach().contiguous()
-                with _timing.span("sage_dgrad_fused", 0, 0):
-                    rc = lib.ngnn_sage_dgrad_fused(
-                        _lib.ptr(dy), dy.stride(0), _lib.ptr(ymask),
-                        ymask.stride(0) if ymask is not None else Fo, yscale, _lib.ptr(wlc),
-                        _lib.ptr(wrc), Fo, K, _lib.ptr(block.rowptr), _lib.ptr(block.col), N,
-                        bptr(i + 1), bptr(i), red, _lib.ptr(h_in), h_in.stride(0), _lib.ptr(agg),
-                        agg.stride(0), _lib.ptr(dh), dh.stride(0), int(i == 0), stream)
-                _lib.check(rc, "ngnn_sage_dgrad_fused")
-                dy = dh
-                continue
-            # dgrad GEMM: [dz W_l | dz W_r] on rows < R (ReLU/dropout backward in the staging)
-            pk = pack_dgrad_weight(wl, wr)
-            dg = torch.empty(N, 2 * K, dtype=torch.float32, device=dev)
-            with _timing.span("sage_dgrad", 0, 0):
-                _gemm_layer(dy, Fo, N, None, "mean", None, pk, None, 2 * K, dg, False, 0.0, 0,
-                            n_rows_dev=bptr(i + 1), xmask=ymask, xscale=yscale)
-            dh = torch.empty(N, K, dtype=torch.float32, device=dev)
-            if deterministic:
-                gws = _workspace(dev, "dgrad", lib.ngnn_sage_dgrad_workspace_bytes(N, K, red))
-                with _timing.span("sage_dgrad_gather", 0, 0):
-                    rc = lib.ngnn_sage_dgrad_gather(
-                        _lib.ptr(dg), 2 * K, _lib.ptr(dg) + 4 * K, 2 * K, _lib.ptr(block.rowptr),
-                        _lib.ptr(block.col), _lib.ptr(t.rowptr), _lib.ptr(t.col), N, bptr(i + 1),
-                        bptr(i), K, red, _lib.ptr(h_in), h_in.stride(0), _lib.ptr(agg),
-                        agg.stride(0), _lib.ptr(dh), dh.stride(0), int(i == 0), _lib.ptr(gws),
-                        gws.numel(), stream)
-                _lib.check(rc, "ngnn_sage_dgrad_gather")
-            else:
-                with _timing.span("sage_dgrad_scatter", 0, 0):
-                    rc = lib.ngnn_sage_dgrad_scatter(
-                        _lib.ptr(dg), 2 * K, _lib.ptr(dg) + 4 * K, 2 * K, _lib.ptr(block.rowptr),
-                        _lib.ptr(block.col), N, bptr(i + 1), bptr(i), K, red, _lib.ptr(h_in),
-                        h_in.stride(0), _lib.ptr(agg), agg.stride(0), _lib.ptr(dh), dh.stride(0),
-                        int(i == 0), stream)
-                _lib.check(rc, "ngnn_sage_dgrad_scatter")
-            dy = dh
+            dy = _layer_dgrad(lib, stream, block, dy, ymask, yscale, wl, wr, red, deterministic, h_in, agg,
+                              bp[i + 1], bp[i], int(i == 0))
         dx = dy if (need_dx and L > 0) else None
         return (dx, None, None, None, None, None, None, None, None, *grads)
 

@@ -584,9 +584,11 @@ def test_3layer_h256_backward_gemm_scatter_path():
     and 100 -> 256 layers' input gradients run the dgrad GEMM + scatter
     (weights too large for the fused kernel's LDS); every gradient against
     the oracle."""
-    from ngnn.fused import _dgrad_fused_ok
+    from ngnn import _lib
     from ngnn.loader import sample_block
-    assert not _dgrad_fused_ok(256, 256) and not _dgrad_fused_ok(256, 100)
+    route = _lib.load().ngnn_sage_dgrad_route
+    assert route(256, 256, _lib.REDUCE["mean"], 0) == _lib.DGRAD_GEMM_SCATTER
+    assert route(256, 100, _lib.REDUCE["mean"], 0) == _lib.DGRAD_GEMM_SCATTER
     g = _graph("ogbn-products", scale=0.01)
     b = sample_block(g, g.train_idx[:256], [8, 5, 3], seed=5)
     torch.manual_seed(7)

@@ -447,7 +447,7 @@ def test_dgrad_lowdim_abi(Fo, K, reduce, masked):
 
 def test_dgrad_lowdim_shape_envelope():
     """Weight images past the LDS budget are refused with NGNN_E_SHAPE (the
-    backward then takes ngnn_sage_dgrad_fused)."""
+    backward asks ngnn_sage_dgrad_route, which sends no such shape here)."""
     from ngnn import _lib
     lib = _lib.load()
     N, Fo, K = 64, 47, 500
