@@ -776,6 +776,153 @@ Ws3 ws3_layout(int64_t n_rows, int64_t K0, int64_t F1) {
     return w;
 }
 
+// ---------------------------------------------------------------- host half
+// ngnn_sage2_bwd's arguments, in the ABI's order: the entry fills it once, by
+// position, and the steps below take it.
+struct Sage2Bwd {
+    const float *dy;
+    int64_t ldy, F1;
+    const float *wl1, *wr1;
+    int64_t ldw1;
+    const float *h;
+    int64_t ldh;
+    float yscale;
+    const float *x;
+    const float *const *x_dev;
+    const int64_t *xrow;
+    const int64_t *const *xrow_dev;
+    int64_t x_rows, ldx, K0;
+    const float *agg0;
+    int64_t ld_agg;
+    const int32_t *rowptr, *col;
+    int64_t n_rows;
+    const int32_t *r_ptr, *rnext_ptr;
+    int reduce;
+    float *dwl1, *dbl1, *dwr1, *dwl0, *dbl0, *dwr0;
+    const float *g_pre;
+    const ngnn_adam_fold *adam;
+    void *ws;
+    size_t ws_bytes;
+    // (ABI 18: dW_r0 and dW_r1 both NULL -- a root-free stack, SimpleGCN's
+    // W_r = 0: x is not read and may be NULL; wr1 is still read -- zeros)
+    bool root() const { return dwr0 || dwr1; }
+    bool indexed() const { return xrow || xrow_dev; }
+    int C4() const { return static_cast<int>((F1 + 3) & ~int64_t{3}); }
+};
+
+// Every argument error of the entry, before any launch.  The order of the
+// checks decides which code a call with several faults gets: part of the
+// contract (tests/test_sage2_args_cpu.py restates it).
+int sage2_bwd_check(const Sage2Bwd &B) {
+    NGNN_RETURN_IF(B.reduce != NGNN_REDUCE_MEAN && B.reduce != NGNN_REDUCE_SUM, NGNN_E_ARG);
+    NGNN_RETURN_IF(B.F1 <= 0 || B.F1 > 48 || B.K0 <= 0 || B.K0 > 128 || B.K0 % 4 != 0, NGNN_E_SHAPE);
+    NGNN_RETURN_IF(B.n_rows < 0 || !fits_i32(B.n_rows), NGNN_E_RANGE);
+    const bool root = B.root(), indexed = B.indexed();
+    NGNN_RETURN_IF(!B.dy || !B.wl1 || !B.wr1 || !B.h || (root && !B.x && !B.x_dev) || !B.agg0 || !B.rowptr ||
+                       !B.col || !B.r_ptr || !B.rnext_ptr || !B.dwl1 || !B.dbl1 || (root && (!B.dwr1 || !B.dwr0)) ||
+                       !B.dwl0 || !B.dbl0 || !B.ws,
+                   NGNN_E_ARG);
+    NGNN_RETURN_IF(!root && indexed, NGNN_E_ARG);
+    NGNN_RETURN_IF(B.ldy < B.F1 || B.ldw1 < 256 || B.ldh < 256 || B.ldh % 4 != 0 || B.ldx < B.K0 || B.ldx % 4 != 0 ||
+                       B.ld_agg < B.K0 || B.ld_agg % 4 != 0,
+                   NGNN_E_SHAPE);
+    NGNN_RETURN_IF((B.x && !aligned(B.x, 16)) || !aligned(B.h, 16) || !aligned(B.agg0, 16) || !aligned(B.ws, 256) ||
+                       (B.g_pre && !aligned(B.g_pre, 16)),
+                   NGNN_E_ALIGN);
+    NGNN_RETURN_IF(indexed && B.x_rows <= 0, NGNN_E_ARG);
+    // 32-bit buffer offsets: every operand's live rows within kRangeMax (as
+    // ngnn_sage2_fwd checks; past it the resources would truncate)
+    const int64_t n = B.n_rows;
+    NGNN_RETURN_IF(n * B.ldh * 4 > kRangeMax || n * B.ld_agg * 4 > kRangeMax || n * B.ldy * 4 > kRangeMax ||
+                       std::max(n, indexed ? B.x_rows : 0) * B.ldx * 4 > kRangeMax || n * B.C4() * 4 > kRangeMax,
+                   NGNN_E_RANGE);
+    if (B.adam) {
+        NGNN_RETURN_IF(!B.adam->step, NGNN_E_ARG);
+        for (int k = 0; k < 6; ++k)
+            NGNN_RETURN_IF(!B.adam->param[k] || !B.adam->exp_avg[k] || !B.adam->exp_avg_sq[k], NGNN_E_ARG);
+    }
+    NGNN_RETURN_IF(B.ws_bytes < ws3_layout(B.n_rows, B.K0, B.F1).total, NGNN_E_WORKSPACE);
+    return NGNN_OK;
+}
+
+// k_bwd2's arguments; g and slab are the workspace's pieces
+B2Args bwd2_args(const Sage2Bwd &B, float *g, float *slab) {
+    B2Args b;
+    b.dy = B.dy, b.ldy = B.ldy, b.F1 = static_cast<int>(B.F1);
+    // (g_pre: the forward's loss head scattered it already -- the workspace's
+    // g stays zero, and the reduce's clearing blocks have nothing to do)
+    b.g = B.g_pre ? B.g_pre : g, b.C4 = B.C4();
+    b.wr1 = B.wr1, b.wl1 = B.wl1, b.ldw1 = B.ldw1, b.h = B.h, b.ldh = B.ldh, b.yscale = B.yscale;
+    // |dh| in the scaled units <= 96 2^30 (two operands of max < 2^15, 96
+    // terms); dz0 = dh yscale must stay below fp16's 2^16 after 2^-e_dz
+    int e = 0;
+    (void)std::frexp(std::max(B.yscale, 1.0f), &e);  // yscale <= 2^e
+    b.e_dz = 21 + e;
+    b.x = B.x, b.x_dev = B.x_dev, b.xrow = B.xrow, b.xrow_dev = B.xrow_dev, b.x_rows = B.x_rows, b.ldx = B.ldx;
+    b.K0 = static_cast<int>(B.K0), b.agg = B.agg0, b.ld_agg = B.ld_agg, b.rowptr = B.rowptr;
+    b.n_rows = static_cast<int>(B.n_rows), b.r_ptr = B.r_ptr, b.rn_ptr = B.rnext_ptr;
+    b.slab = slab, b.S = B2_S;
+    b.step_inc = B.adam ? B.adam->step : nullptr;
+    b.gate = B.adam ? B.adam->gate : nullptr;
+    b.gate_gen = B.adam ? B.adam->gate_gen : nullptr;
+    return b;
+}
+
+#ifdef NGNN_B2_DBG_BUILD
+constexpr bool kB2DbgBuild = true;
+#else
+constexpr bool kB2DbgBuild = false;
+#endif
+
+// The one k_bwd2 launch.  Instantiated: XR x KT {4, 7, 8} x LAG with a root
+// term; root-free with XR false only (x is not read, and sage2_bwd_check
+// refuses an index there); DBG 1 (profiling builds, NGNN_B2_DBG=1) on the
+// rooted lagged kernels only -- the `if constexpr` keeps the others out.
+// (This nesting emits the kernels in the order they have always had in the
+// object file.)
+int launch_bwd2(const Sage2Bwd &B, const B2Args &b, hipStream_t st) {
+    // (A/B switch, read once; default lagged: measured 43.8 vs 44.6 us per
+    // call, tools/bwd2_micro.py)
+    static const bool lag = env_not_zero("NGNN_B2_LAG");
+    static const int dbg_env = kB2DbgBuild ? env_int("NGNN_B2_DBG", 0) : 0;
+    const bool root = B.root();
+    const int dbg = (root && lag && dbg_env == 1) ? 1 : 0;
+    // (+ the chunk maxima: [2][8] float4)
+    const size_t lds = static_cast<size_t>(2) * BUF * 2 + 2 * 256 * 4 + 480 * 4 + 2 * 8 * 16;
+    with_const<1, 0>(B.indexed(), [&](auto xr_c) {
+    with_const<4, 7, 8>(B.K0 <= 64 ? 4 : B.K0 <= 112 ? 7 : 8, [&](auto kt_c) {
+    with_const<0, 1>(root, [&](auto root_c) {
+    with_const<1, 0>(lag, [&](auto lag_c) {
+    with_const<1, 0>(dbg, [&](auto dbg_c) {
+        constexpr bool ROOT = decltype(root_c)::value != 0, LAG = decltype(lag_c)::value != 0;
+        constexpr bool XR = decltype(xr_c)::value != 0 && ROOT;  // (root-free: x is not read)
+        constexpr int DBG = decltype(dbg_c)::value;
+        if constexpr (DBG == 0 || (kB2DbgBuild && ROOT && LAG)) {
+            constexpr auto fn = k_bwd2<XR, decltype(kt_c)::value, LAG, ROOT, DBG>;
+            max_dynamic_lds_once<fn>(lds);
+            hipLaunchKernelGGL(fn, dim3(B2_S * B2_NCH), dim3(B2_THREADS), lds, st, b);
+        }
+    }); }); }); }); });
+    return launch_status();
+}
+
+// ngnn_adam_fold in the reduce's tensor order (zeros without one)
+AdamFold adam_fold(const ngnn_adam_fold *adam) {
+    AdamFold af{};
+    if (!adam) return af;
+    // (the header's order dW_l1, db1, dW_r1, dW_l0, db0, dW_r0 -> the reduce's)
+    static const int ord[6] = {5, 3, 4, 2, 0, 1};
+    for (int k = 0; k < 6; ++k) {
+        af.p[k] = adam->param[ord[k]];
+        af.m[k] = adam->exp_avg[ord[k]];
+        af.v[k] = adam->exp_avg_sq[ord[k]];
+    }
+    af.step = adam->step;
+    af.lr = adam->lr, af.b1 = adam->beta1, af.b2 = adam->beta2, af.eps = adam->eps, af.wd = adam->weight_decay;
+    af.gate = adam->gate, af.gate_gen = adam->gate_gen;
+    return af;
+}
+
 }  // namespace
 }  // namespace ngnn
 
@@ -794,145 +941,26 @@ extern "C" int ngnn_sage2_bwd(const float *dy, int64_t ldy, int64_t F1, const fl
                               const int32_t *rnext_ptr, int reduce, float *dwl1, float *dbl1, float *dwr1,
                               float *dwl0, float *dbl0, float *dwr0, const float *g_pre,
                               const ngnn_adam_fold *adam, void *ws, size_t ws_bytes, void *stream) {
-    NGNN_RETURN_IF(reduce != NGNN_REDUCE_MEAN && reduce != NGNN_REDUCE_SUM, NGNN_E_ARG);
-    NGNN_RETURN_IF(F1 <= 0 || F1 > 48 || K0 <= 0 || K0 > 128 || K0 % 4 != 0, NGNN_E_SHAPE);
-    NGNN_RETURN_IF(n_rows < 0 || !fits_i32(n_rows), NGNN_E_RANGE);
-    // (ABI 18: dW_r0 and dW_r1 both NULL -- a root-free stack, SimpleGCN's
-    // W_r = 0: x is not read and may be NULL; wr1 is still read -- zeros)
-    const bool root = dwr0 || dwr1;
-    NGNN_RETURN_IF(!dy || !wl1 || !wr1 || !h || (root && !x && !x_dev) || !agg0 || !rowptr || !col || !r_ptr ||
-                       !rnext_ptr || !dwl1 || !dbl1 || (root && (!dwr1 || !dwr0)) || !dwl0 || !dbl0 || !ws,
-                   NGNN_E_ARG);
-    NGNN_RETURN_IF(!root && (xrow || xrow_dev), NGNN_E_ARG);
-    NGNN_RETURN_IF(ldy < F1 || ldw1 < 256 || ldh < 256 || ldh % 4 != 0 || ldx < K0 || ldx % 4 != 0 ||
-                       ld_agg < K0 || ld_agg % 4 != 0,
-                   NGNN_E_SHAPE);
-    NGNN_RETURN_IF((x && !aligned(x, 16)) || !aligned(h, 16) || !aligned(agg0, 16) || !aligned(ws, 256) ||
-                       (g_pre && !aligned(g_pre, 16)),
-                   NGNN_E_ALIGN);
-    const bool indexed = xrow || xrow_dev;
-    NGNN_RETURN_IF(indexed && x_rows <= 0, NGNN_E_ARG);
-    {
-        // 32-bit buffer offsets: every operand's live rows under 3.75 GiB (as
-        // ngnn_sage2_fwd checks; past it the resources would truncate)
-        const int64_t lim = 0xF0000000ll - 4096, C4 = (F1 + 3) & ~int64_t{3};
-        NGNN_RETURN_IF(n_rows * ldh * 4 > lim || n_rows * ld_agg * 4 > lim || n_rows * ldy * 4 > lim ||
-                           std::max(n_rows, indexed ? x_rows : 0) * ldx * 4 > lim || n_rows * C4 * 4 > lim,
-                       NGNN_E_RANGE);
-    }
-    if (adam) {
-        NGNN_RETURN_IF(!adam->step, NGNN_E_ARG);
-        for (int k = 0; k < 6; ++k)
-            NGNN_RETURN_IF(!adam->param[k] || !adam->exp_avg[k] || !adam->exp_avg_sq[k], NGNN_E_ARG);
-    }
-    const Ws3 L = ws3_layout(n_rows, K0, F1);
-    NGNN_RETURN_IF(ws_bytes < L.total, NGNN_E_WORKSPACE);
+    const Sage2Bwd B{dy, ldy, F1, wl1, wr1, ldw1, h, ldh, yscale, x, x_dev, xrow, xrow_dev, x_rows, ldx, K0, agg0,
+                     ld_agg, rowptr, col, n_rows, r_ptr, rnext_ptr, reduce, dwl1, dbl1, dwr1, dwl0, dbl0, dwr0,
+                     g_pre, adam, ws, ws_bytes};
+    if (const int rc = sage2_bwd_check(B)) return rc;
     hipStream_t st = as_stream(stream);
-    char *wsb = static_cast<char *>(ws);
-    float *g = reinterpret_cast<float *>(wsb + L.g);
-    float *slab = reinterpret_cast<float *>(wsb + L.slab);
-    const int C4 = static_cast<int>((F1 + 3) & ~int64_t{3});
-    // (g_pre: the forward's loss head scattered it already -- the workspace's
-    // g stays zero, and its clearing blocks below have nothing to do)
+    const Ws3 L = ws3_layout(n_rows, K0, F1);
+    float *g = reinterpret_cast<float *>(static_cast<char *>(ws) + L.g);
+    float *slab = reinterpret_cast<float *>(static_cast<char *>(ws) + L.slab);
     if (n_rows > 0 && !g_pre) {
         const int rc = lowdim_scatter_launch(dy, ldy, rowptr, col, static_cast<int>(n_rows), r_ptr,
-                                             static_cast<int>(F1), C4, g, reduce == NGNN_REDUCE_MEAN, st);
+                                             static_cast<int>(F1), B.C4(), g, reduce == NGNN_REDUCE_MEAN, st);
         if (rc) return rc;
     }
-    B2Args b;
-    b.dy = dy;
-    b.ldy = ldy;
-    b.F1 = static_cast<int>(F1);
-    b.g = g_pre ? g_pre : g;
-    b.C4 = C4;
-    b.wr1 = wr1;
-    b.wl1 = wl1;
-    b.ldw1 = ldw1;
-    b.h = h;
-    b.ldh = ldh;
-    b.yscale = yscale;
-    // |dh| in the scaled units <= 96 2^30 (two operands of max < 2^15, 96
-    // terms); dz0 = dh yscale must stay below fp16's 2^16 after 2^-e_dz
-    {
-        int e = 0;
-        (void)std::frexp(std::max(yscale, 1.0f), &e);  // yscale <= 2^e
-        b.e_dz = 21 + e;
-    }
-    b.x = x;
-    b.x_dev = x_dev;
-    b.xrow = xrow;
-    b.xrow_dev = xrow_dev;
-    b.x_rows = x_rows;
-    b.ldx = ldx;
-    b.K0 = static_cast<int>(K0);
-    b.agg = agg0;
-    b.ld_agg = ld_agg;
-    b.rowptr = rowptr;
-    b.n_rows = static_cast<int>(n_rows);
-    b.r_ptr = r_ptr;
-    b.rn_ptr = rnext_ptr;
-    b.slab = slab;
-    b.S = B2_S;
-    b.step_inc = adam ? adam->step : nullptr;
-    b.gate = adam ? adam->gate : nullptr;
-    b.gate_gen = adam ? adam->gate_gen : nullptr;
-    // (+ the chunk maxima: [2][8] float4)
-    const size_t lds = static_cast<size_t>(2) * BUF * 2 + 2 * 256 * 4 + 480 * 4 + 2 * 8 * 16;
-    static const bool lag = [] {
-        const char *v = std::getenv("NGNN_B2_LAG");  // (A/B switch, read once; default lagged: measured
-        return !(v && v[0] == '0');                  // 43.8 vs 44.6 us per call, tools/bwd2_micro.py)
-    }();
-    auto go = [&](auto xr_c, auto kt_c) {
-        constexpr bool XRv = decltype(xr_c)::value;
-        constexpr int KTv = decltype(kt_c)::value;
-        auto fn = !root ? (lag ? k_bwd2<false, KTv, true, false> : k_bwd2<false, KTv, false, false>)
-                        : lag ? k_bwd2<XRv, KTv, true> : k_bwd2<XRv, KTv, false>;
-#ifdef NGNN_B2_DBG_BUILD
-        static const int dbg = [] {
-            const char *v = std::getenv("NGNN_B2_DBG");
-            return v ? std::atoi(v) : 0;
-        }();
-        if (root && lag && dbg == 1) fn = k_bwd2<XRv, KTv, true, true, 1>;
-#endif
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  160 * 1024);  // (cheap; the function varies with root / lag)
-        hipLaunchKernelGGL(fn, dim3(B2_S * B2_NCH), dim3(B2_THREADS), lds, st, b);
-        return launch_status();
-    };
-    auto by_kt = [&](auto xr_c) {
-        if (K0 <= 64) return go(xr_c, std::integral_constant<int, 4>{});
-        if (K0 <= 112) return go(xr_c, std::integral_constant<int, 7>{});
-        return go(xr_c, std::integral_constant<int, 8>{});
-    };
-    int rc = indexed ? by_kt(std::true_type{}) : by_kt(std::false_type{});
-    if (rc) return rc;
-    const int64_t total = b2_slab_floats(static_cast<int>(K0), static_cast<int>(F1));
-    const int n_red = static_cast<int>(ceil_div(total, 256));
+    if (const int rc = launch_bwd2(B, bwd2_args(B, g, slab), st)) return rc;
+    const int n_red = static_cast<int>(ceil_div(b2_slab_floats(static_cast<int>(K0), static_cast<int>(F1)), 256));
     const int n_clr = g_pre ? 0 : 64;
-    AdamFold af{};
-    if (adam) {
-        // (the header's order dW_l1, db1, dW_r1, dW_l0, db0, dW_r0 -> the reduce's)
-        static const int ord[6] = {5, 3, 4, 2, 0, 1};
-        for (int k = 0; k < 6; ++k) {
-            af.p[k] = adam->param[ord[k]];
-            af.m[k] = adam->exp_avg[ord[k]];
-            af.v[k] = adam->exp_avg_sq[ord[k]];
-        }
-        af.step = adam->step;
-        af.lr = adam->lr;
-        af.b1 = adam->beta1;
-        af.b2 = adam->beta2;
-        af.eps = adam->eps;
-        af.wd = adam->weight_decay;
-        af.gate = adam->gate;
-        af.gate_gen = adam->gate_gen;
-        hipLaunchKernelGGL(k_bwd2_reduce<true>, dim3(n_red + n_clr), dim3(256), 0, st, slab, B2_S,
-                           static_cast<int>(K0), static_cast<int>(F1), dwr0, dwl0, dbl0, dwr1, dwl1, dbl1, g, C4,
-                           static_cast<int>(n_rows), r_ptr, rnext_ptr, n_red, af);
-    } else {
-        hipLaunchKernelGGL(k_bwd2_reduce<false>, dim3(n_red + n_clr), dim3(256), 0, st, slab, B2_S,
-                           static_cast<int>(K0), static_cast<int>(F1), dwr0, dwl0, dbl0, dwr1, dwl1, dbl1, g, C4,
-                           static_cast<int>(n_rows), r_ptr, rnext_ptr, n_red, af);
-    }
+    with_const<1, 0>(adam != nullptr, [&](auto adam_c) {
+        hipLaunchKernelGGL(k_bwd2_reduce<decltype(adam_c)::value != 0>, dim3(n_red + n_clr), dim3(256), 0, st, slab,
+                           B2_S, static_cast<int>(K0), static_cast<int>(F1), dwr0, dwl0, dbl0, dwr1, dwl1, dbl1, g,
+                           B.C4(), static_cast<int>(n_rows), r_ptr, rnext_ptr, n_red, adam_fold(adam));
+    });
     return launch_status();
 }

@@ -1083,47 +1083,9 @@ __global__ __launch_bounds__(F2_WAVES * 64) void k_fwd2x(G2Args g, F2Args f) {
     fwd2_body<C0, NT1, DM, XR, T16, 0, ROOT>(f);
 }
 
-template <int C0, int NT1, int DM, bool XR, int DBG = 0, bool T16 = false, bool ROOT = true>
-int launch_fwd2(const F2Args &a, int grid, hipStream_t st) {
-    auto fn = k_fwd2<C0, NT1, DM, XR, T16, DBG, ROOT>;
-    const size_t lds = static_cast<size_t>(2) * (F2_HID / 32) * 2 * 64 * 16 +
-                       static_cast<size_t>(2) * 2 * F2_ROWS * (32 * C0 + 16) * 2 + 2 * F2_ROWS * 4 +
-                       (F2_HID + 16 * NT1) * 4 + 2 * F2_ROWS * 16 * NT1 * 4 + 2 * F2_ROWS * F2_WAVES * 4 + 64 * 4;
-    static bool attr_set = false;  // benign race: idempotent
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  160 * 1024);
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(fn, dim3(grid), dim3(F2_WAVES * 64), lds, st, a);
-    return launch_status();
-}
-
-template <int C0, int NT1, int DM, bool XR, bool T16 = false, bool ROOT = true>
-int launch_fwd2x(const G2Args &g, const F2Args &a, int grid, hipStream_t st) {
-    auto fn = k_fwd2x<C0, NT1, DM, XR, T16, ROOT>;
-    const size_t lds = static_cast<size_t>(2) * (F2_HID / 32) * 2 * 64 * 16 +
-                       static_cast<size_t>(2) * 2 * F2_ROWS * (32 * C0 + 16) * 2 + 2 * F2_ROWS * 4 +
-                       (F2_HID + 16 * NT1) * 4 + 2 * F2_ROWS * 16 * NT1 * 4 + 2 * F2_ROWS * F2_WAVES * 4 + 64 * 4;
-    static bool attr_set = false;  // benign race: idempotent
-    if (!attr_set) {
-        // (the edge phase's static LDS counts against the same 160 KiB: the
-        // dynamic maximum is exactly what the main phase takes -- a 160 KiB
-        // request is refused, and the launch then fails)
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-        if (e != hipSuccess) return static_cast<int>(e);
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(fn, dim3(grid), dim3(F2_WAVES * 64), lds, st, g, a);
-    return launch_status();
-}
-
-template <int C0, int DBG = 0>
-int launch_edge_nb(const G2Args &a, int grid, hipStream_t st) {
-    hipLaunchKernelGGL((k_edge_nb<C0, DBG>), dim3(grid), dim3(F2_WAVES * 64), 0, st, a);
-    return launch_status();
-}
+// ---------------------------------------------------------------- host half
+// (the descriptor, the checks, the argument builders
+// and the one kernel selector)
 
 // workspace layout (256-B aligned pieces)
 struct Ws2 {
@@ -1144,6 +1106,235 @@ Ws2 ws2_layout(int64_t K0, int64_t F1, int64_t n_rows) {
     w.z = take(static_cast<size_t>(rows16) * NT1 * 16 * 4);
     w.total = off;
     return w;
+}
+
+// ngnn_sage2_supported admits 96 < K0 <= 128 and 32 < F1 <= 48 only, so every
+// call has four 32-deep chunks of K0 and three 16-wide tiles of F1: the one
+// shape the kernels are instantiated for.
+constexpr int F2_C0 = 4, F2_NT1 = 3;
+
+// ngnn_sage2_fwd's arguments, in the ABI's order: the entry fills it once, by
+// position, and every step below takes it (as LayerFwd, ngnn_device.h).
+struct Sage2Fwd {
+    const float *x;
+    const float *const *x_dev;
+    const int64_t *xrow;
+    const int64_t *const *xrow_dev;
+    int64_t x_rows, ldx, K0, n_rows;
+    const int32_t *n_rows_dev;
+    int64_t n_edge_rows;
+    const int32_t *n_edge_rows_dev;
+    const int32_t *rowptr, *col, *col_x;
+    int reduce;
+    const float *wl0, *bl0, *wr0;
+    int64_t ldw0, H;
+    const float *wl1, *bl1, *wr1;
+    int64_t ldw1, F1;
+    float p_drop;
+    uint64_t seed;
+    const uint64_t *seed_dev;
+    float *h;
+    int64_t ldh, h_rows;
+    const int32_t *h_rows_dev;
+    float *agg0;
+    int64_t ld_agg;
+    float *out;
+    int64_t ldo;
+    const ngnn_xent_head *head;
+    int stages;
+    void *ws;
+    size_t ws_bytes;
+    bool indexed() const { return xrow || xrow_dev; }
+    // does this call's edge launch run (on its own or as the fused launch's
+    // edge phase)?  The head's g zeroing, label count and seed-edge counts
+    // ride on it.
+    bool edge_runs() const { return (stages & NGNN_SAGE2_EDGE) && n_edge_rows > 0; }
+    int64_t C4() const { return (F1 + 3) & ~int64_t{3}; }  // the head's g row, floats
+    int64_t ldz() const { return 16 * F2_NT1; }
+};
+
+// Every argument error of the entry, before any launch.  The order of the
+// checks decides which code a call with several faults gets, and n_rows == 0
+// answers NGNN_OK before any pointer is looked at: part of the contract
+// (tests/test_sage2_args_cpu.py restates it).  NGNN_OK with n_rows == 0 means
+// "nothing to do", which the entry tests for itself.
+int sage2_fwd_check(const Sage2Fwd &S) {
+    NGNN_RETURN_IF(!ngnn_sage2_supported(S.K0, S.H, S.F1, S.reduce), NGNN_E_SHAPE);
+    NGNN_RETURN_IF(S.n_rows < 0 || S.n_edge_rows < 0 || S.h_rows < 0, NGNN_E_ARG);
+    NGNN_RETURN_IF(S.p_drop < 0.0f || !(S.p_drop <= 1.0f), NGNN_E_ARG);
+    NGNN_RETURN_IF(S.stages <= 0 || S.stages > NGNN_SAGE2_ALL, NGNN_E_ARG);
+    NGNN_RETURN_IF(S.ldx < S.K0 || S.ldx % 4 != 0 || S.ldw0 < S.K0 || S.ldw0 % 4 != 0 || S.ldw1 < S.H ||
+                       S.ldw1 % 4 != 0 || S.ldh < S.H || S.ldh % 4 != 0 || S.ld_agg < S.K0 || S.ld_agg % 4 != 0 ||
+                       S.ldo != S.F1,
+                   NGNN_E_SHAPE);
+    NGNN_RETURN_IF(!fits_i32(S.n_rows), NGNN_E_RANGE);
+    const bool indexed = S.indexed();
+    NGNN_RETURN_IF(indexed && (S.x_rows <= 0 || !S.col_x), NGNN_E_ARG);
+    if (S.n_rows == 0) return NGNN_OK;
+    // (wr0 NULL, ABI 17: no root term -- GCNConv(normalize=False)'s layer;
+    // not with the fused x[n_id] gather)
+    NGNN_RETURN_IF(!S.wr0 && indexed, NGNN_E_ARG);
+    NGNN_RETURN_IF((!S.x && !S.x_dev) || !S.rowptr || (!S.col && S.n_edge_rows > 0) || !S.wl0 || !S.bl0 || !S.wl1 ||
+                       !S.bl1 || !S.wr1 || !S.h || !S.agg0 || !S.out || !S.ws,
+                   NGNN_E_ARG);
+    NGNN_RETURN_IF((S.x && !aligned(S.x, 16)) || !aligned(S.h, 16) || !aligned(S.out, 16) || !aligned(S.agg0, 16) ||
+                       !aligned(S.bl0, 16) || !aligned(S.wr0, 16) || !aligned(S.wl0, 16) || !aligned(S.wr1, 16) ||
+                       !aligned(S.wl1, 16) || !aligned(S.ws, 256),
+                   NGNN_E_ALIGN);
+    // 32-bit buffer offsets: every operand within kRangeMax
+    const int64_t n = S.n_rows;
+    NGNN_RETURN_IF(std::max(n, indexed ? S.x_rows : 0) * S.ldx * 4 > kRangeMax || n * S.ldh * 4 > kRangeMax ||
+                       n * S.ld_agg * 4 > kRangeMax || n * S.ldo * 4 > kRangeMax || n * F2_HID * 4 > kRangeMax,
+                   NGNN_E_RANGE);
+    NGNN_RETURN_IF(S.ws_bytes < ws2_layout(S.K0, S.F1, n).total, NGNN_E_WORKSPACE);
+    if (const ngnn_xent_head *hd = S.head) {
+        NGNN_RETURN_IF(!hd->y || !hd->loss || !hd->count || !hd->dy || !hd->ws, NGNN_E_ARG);
+        NGNN_RETURN_IF(hd->B <= 0 || hd->B > n || hd->ldd < S.F1, NGNN_E_ARG);
+        NGNN_RETURN_IF(hd->g && (hd->g_rows < 0 || hd->g_rows > n), NGNN_E_ARG);
+        NGNN_RETURN_IF(hd->ws_bytes < ngnn_xent_head_workspace_bytes(hd->B), NGNN_E_WORKSPACE);
+        NGNN_RETURN_IF(!aligned(hd->ws, 16) || (hd->g && !aligned(hd->g, 16)), NGNN_E_ALIGN);
+        NGNN_RETURN_IF(hd->g && hd->g_rows * S.C4() * 4 > kRangeMax, NGNN_E_RANGE);
+    }
+    return NGNN_OK;
+}
+
+// k_edge_nb's arguments (the fused launch's edge phase alike); nb is the
+// workspace's piece.  The head's parts that ride on the edge launch: g's
+// zeroing, the valid-label count (head->ws + 4) and the seed-edge counts.
+G2Args edge_args(const Sage2Fwd &S, float *nb) {
+    const ngnn_xent_head *hd = S.head;
+    G2Args g{};
+    g.x = S.x, g.x_dev = S.x_dev, g.ldx = S.ldx, g.K0 = static_cast<int>(S.K0);
+    g.n_rows = static_cast<int>(S.n_rows), g.n_rows_dev = S.n_rows_dev;
+    g.n_edge = static_cast<int>(std::min(S.n_edge_rows, S.n_rows)), g.n_edge_dev = S.n_edge_rows_dev;
+    g.rowptr = S.rowptr, g.col = S.col, g.col_x = S.indexed() ? S.col_x : nullptr, g.x_rows = S.x_rows;
+    g.mean = S.reduce == NGNN_REDUCE_MEAN;
+    g.wl0 = S.wl0, g.ldw0 = S.ldw0, g.agg = S.agg0, g.ld_agg = S.ld_agg, g.nb = nb;
+    // (agg0 has n_rows rows -- the saved aggregate's and nb's rows are whole
+    // edge tiles, capped at n_rows; nb itself has ceil16(n_rows))
+    g.cap_rows = S.n_rows;
+    g.gz_ld = static_cast<int>(S.C4());
+    if (hd) {
+        g.gz = hd->g, g.gz_rows = static_cast<int>(hd->g_rows), g.gz_rows_dev = hd->g_rows_dev;
+        g.cnt_y = hd->y, g.cnt_B = static_cast<int>(hd->B), g.cnt_ignore = hd->ignore_index;
+        g.cnt_out = reinterpret_cast<float *>(static_cast<char *>(hd->ws) + 4);
+        g.scnt_base = hd->g ? hd->src_count : nullptr, g.scnt_stride = static_cast<int>(hd->g_rows);
+    }
+    return g;
+}
+
+// k_fwd2's arguments (the fused launch's main phase alike); nb and z are the
+// workspace's pieces
+F2Args main_args(const Sage2Fwd &S, const float *nb, float *z) {
+    F2Args f;
+    f.x = S.x, f.x_dev = S.x_dev, f.ldx = S.ldx, f.K0 = static_cast<int>(S.K0);
+    f.xrow = S.xrow, f.xrow_dev = S.xrow_dev, f.x_rows = S.x_rows;
+    f.n_rows = static_cast<int>(S.n_rows), f.n_rows_dev = S.n_rows_dev;
+    f.n_edge = static_cast<int>(std::min(S.n_edge_rows, S.n_rows)), f.n_edge_dev = S.n_edge_rows_dev;
+    f.nb = nb, f.cap_rows = ceil_div(S.n_rows, 16) * 16;
+    f.wr0 = S.wr0, f.ldw0 = S.ldw0, f.wr1 = S.wr1, f.wl1 = S.wl1, f.ldw1 = S.ldw1, f.b0 = S.bl0, f.b1 = S.bl1;
+    f.drop = make_dropout(S.p_drop, S.seed), f.seed_dev = S.seed_dev;
+    f.h = S.h, f.ldh = S.ldh, f.h_rows = static_cast<int>(std::min(S.h_rows, S.n_rows)), f.h_rows_dev = S.h_rows_dev;
+    f.out = S.out, f.ldo = S.ldo, f.z = z, f.ldz = S.ldz(), f.F1 = static_cast<int>(S.F1);
+    return f;
+}
+
+// the NARROW launch's loss head (S.head non-null)
+NarrowHead narrow_head(const Sage2Fwd &S) {
+    const ngnn_xent_head *hd = S.head;
+    NarrowHead nh{};
+    nh.y = hd->y, nh.B = static_cast<int>(hd->B), nh.ignore = hd->ignore_index;
+    nh.loss = hd->loss, nh.count = hd->count, nh.dy = hd->dy, nh.ldd = hd->ldd;
+    nh.g = hd->g, nh.ldg = static_cast<int>(S.C4());
+    nh.ticket = static_cast<uint32_t *>(hd->ws);
+    nh.part = reinterpret_cast<float *>(static_cast<char *>(hd->ws) + 256);
+    // the label count and the seed-edge counts from this call's edge launch
+    // (edge_args), else counted there / none
+    const float *cnt = reinterpret_cast<const float *>(static_cast<char *>(hd->ws) + 4);
+    nh.cnt_in = S.edge_runs() ? cnt : nullptr;
+    if (S.edge_runs() && hd->g) nh.scnt_base = hd->src_count, nh.scnt_stride = static_cast<int>(hd->g_rows);
+#ifdef NGNN_FWD2_DBG_BUILD
+    if (const char *d = getenv("NGNN_HEAD_DBG")) {
+        nh.dbg = atoi(d);
+        if (nh.dbg & 16) nh.cnt_in = cnt;
+    }
+#endif
+    return nh;
+}
+
+// dynamic LDS of fwd2_body (k_fwd2, and k_fwd2x's main phase -- its edge
+// phase's LDS is static and counts against the same 160 KiB, so the limit the
+// launchers ask for is exactly this: a flat 160 KiB is refused there)
+template <int C0, int NT1>
+constexpr size_t fwd2_lds_bytes() {
+    return static_cast<size_t>(2) * (F2_HID / 32) * 2 * 64 * 16 +
+           static_cast<size_t>(2) * 2 * F2_ROWS * (32 * C0 + 16) * 2 + 2 * F2_ROWS * 4 + (F2_HID + 16 * NT1) * 4 +
+           2 * F2_ROWS * 16 * NT1 * 4 + 2 * F2_ROWS * F2_WAVES * 4 + 64 * 4;
+}
+
+// The time-attribution variants of profiling builds (NGNN_FWD2_DBG_BUILD):
+// the DBG values instantiated, 0 (the product kernel) last as the default.
+#ifdef NGNN_FWD2_DBG_BUILD
+#define F2_EDGE_DBG 1, 2, 3, 4, 6, 7, 8, 16, 23, 24, 0
+#define F2_MAIN_DBG 1, 2, 3, 4, 8, 15, 16, 32, 64, 0
+#else
+#define F2_EDGE_DBG 0
+#define F2_MAIN_DBG 0
+#endif
+
+// one workgroup per CU walking its 16-row tiles
+int tile_grid(int64_t rows) {
+    return static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(num_cus(), ceil_div(rows, 16))));
+}
+
+inline int dropout_mode(const Dropout &d) { return d.thresh == 0 ? 0 : d.thresh == 128u ? 2 : 1; }
+
+// k_edge_nb on its own (the two-launch route)
+int launch_edge(const G2Args &g, int dbg, hipStream_t st) {
+    with_const<F2_EDGE_DBG>(dbg, [&](auto dbg_c) {
+        hipLaunchKernelGGL((k_edge_nb<F2_C0, decltype(dbg_c)::value>), dim3(tile_grid(g.n_edge)),
+                           dim3(F2_WAVES * 64), 0, st, g);
+    });
+    return launch_status();
+}
+
+// The main launch: k_fwd2x (fuse: the edge phase g rides along) or k_fwd2,
+// by dropout mode x indexed x T16 x root.  Instantiated: every rooted
+// combination; root-free (wr0 NULL) without the gather and without T16 only
+// (no x rows there; sage2_fwd_check refuses an index); a DBG variant only as
+// k_fwd2<.., DM 2, plain rows, 4 x 32, rooted> -- the `if constexpr` keeps
+// every other combination out, and the run-time values never name one.
+int launch_main(const Sage2Fwd &S, const G2Args &g, const F2Args &f, bool fuse, int dbg, hipStream_t st) {
+    // (K0 <= 112: the 16-deep tail chunk; NGNN_FWD2_T16=0 forces 4 x 32 -- A/B)
+    static const bool t16_ok = env_not_zero("NGNN_FWD2_T16");
+    const bool root = S.wr0 != nullptr;
+    const bool t16 = t16_ok && S.K0 <= 112 && root && !dbg;
+    const int grid = tile_grid(S.n_rows);
+    constexpr size_t lds = fwd2_lds_bytes<F2_C0, F2_NT1>();
+    // (this nesting emits the kernels in the order they have always had in
+    // the object file: root-free first, the dropout mode innermost)
+    with_const<0, 1>(root, [&](auto root_c) {
+    with_const<1, 0>(S.indexed(), [&](auto xr_c) {
+    with_const<1, 0>(fuse, [&](auto fuse_c) {
+    with_const<1, 0>(t16, [&](auto t16_c) {
+    with_const<2, 1, 0>(dropout_mode(f.drop), [&](auto dm_c) {
+    with_const<F2_MAIN_DBG>(dbg, [&](auto dbg_c) {
+        constexpr int DM = decltype(dm_c)::value, DBG = decltype(dbg_c)::value;
+        constexpr bool XR = decltype(xr_c)::value != 0, T16 = decltype(t16_c)::value != 0;
+        constexpr bool ROOT = decltype(root_c)::value != 0, FUSED = decltype(fuse_c)::value != 0;
+        if constexpr ((ROOT || (!XR && !T16)) && (DBG == 0 || (DM == 2 && !XR && !T16 && ROOT && !FUSED))) {
+            if constexpr (FUSED) {
+                constexpr auto fn = k_fwd2x<F2_C0, F2_NT1, DM, XR, T16, ROOT>;
+                max_dynamic_lds_once<fn>(lds);
+                hipLaunchKernelGGL(fn, dim3(grid), dim3(F2_WAVES * 64), lds, st, g, f);
+            } else {
+                constexpr auto fn = k_fwd2<F2_C0, F2_NT1, DM, XR, T16, DBG, ROOT>;
+                max_dynamic_lds_once<fn>(lds);
+                hipLaunchKernelGGL(fn, dim3(grid), dim3(F2_WAVES * 64), lds, st, f);
+            }
+        }
+    }); }); }); }); }); });
+    return launch_status();
 }
 
 }  // namespace
@@ -1187,249 +1378,49 @@ extern "C" int ngnn_sage2_fwd(const float *x, const float *const *x_dev, const i
                               const int32_t *h_rows_dev, float *agg0, int64_t ld_agg, float *out,
                               int64_t ldo, const ngnn_xent_head *head, int stages, void *ws, size_t ws_bytes,
                               void *stream) {
-    NGNN_RETURN_IF(!ngnn_sage2_supported(K0, H, F1, reduce), NGNN_E_SHAPE);
-    NGNN_RETURN_IF(n_rows < 0 || n_edge_rows < 0 || h_rows < 0, NGNN_E_ARG);
-    NGNN_RETURN_IF(p_drop < 0.0f || !(p_drop <= 1.0f), NGNN_E_ARG);
-    NGNN_RETURN_IF(stages <= 0 || stages > NGNN_SAGE2_ALL, NGNN_E_ARG);
-    NGNN_RETURN_IF(ldx < K0 || ldx % 4 != 0 || ldw0 < K0 || ldw0 % 4 != 0 || ldw1 < H || ldw1 % 4 != 0 || ldh < H || ldh % 4 != 0 ||
-                       ld_agg < K0 || ld_agg % 4 != 0 || ldo != F1,
-                   NGNN_E_SHAPE);
-    NGNN_RETURN_IF(!fits_i32(n_rows), NGNN_E_RANGE);
-    const bool indexed = xrow || xrow_dev;
-    NGNN_RETURN_IF(indexed && (x_rows <= 0 || !col_x), NGNN_E_ARG);
-    if (n_rows == 0) return NGNN_OK;
-    // (wr0 NULL, ABI 17: no root term -- GCNConv(normalize=False)'s layer;
-    // not with the fused x[n_id] gather)
-    NGNN_RETURN_IF(!wr0 && (xrow || xrow_dev), NGNN_E_ARG);
-    NGNN_RETURN_IF((!x && !x_dev) || !rowptr || (!col && n_edge_rows > 0) || !wl0 || !bl0 || !wl1 || !bl1 || !wr1 ||
-                       !h || !agg0 || !out || !ws,
-                   NGNN_E_ARG);
-    NGNN_RETURN_IF((x && !aligned(x, 16)) || !aligned(h, 16) || !aligned(out, 16) || !aligned(agg0, 16) || !aligned(bl0, 16) ||
-                       !aligned(wr0, 16) || !aligned(wl0, 16) || !aligned(wr1, 16) || !aligned(wl1, 16) ||
-                       !aligned(ws, 256),
-                   NGNN_E_ALIGN);
-    // 32-bit buffer offsets: every operand under 3.75 GiB
-    const int64_t lim = 0xF0000000ll - 4096;
-    NGNN_RETURN_IF(std::max(n_rows, indexed ? x_rows : 0) * ldx * 4 > lim || n_rows * ldh * 4 > lim || n_rows * ld_agg * 4 > lim ||
-                       n_rows * ldo * 4 > lim || n_rows * F2_HID * 4 > lim,
-                   NGNN_E_RANGE);
-    const Ws2 L = ws2_layout(K0, F1, n_rows);
-    NGNN_RETURN_IF(ws_bytes < L.total, NGNN_E_WORKSPACE);
-    const int64_t C4 = (F1 + 3) & ~int64_t{3};
-    if (head) {
-        NGNN_RETURN_IF(!head->y || !head->loss || !head->count || !head->dy || !head->ws, NGNN_E_ARG);
-        NGNN_RETURN_IF(head->B <= 0 || head->B > n_rows || head->ldd < F1, NGNN_E_ARG);
-        NGNN_RETURN_IF(head->g && (head->g_rows < 0 || head->g_rows > n_rows), NGNN_E_ARG);
-        NGNN_RETURN_IF(head->ws_bytes < ngnn_xent_head_workspace_bytes(head->B), NGNN_E_WORKSPACE);
-        NGNN_RETURN_IF(!aligned(head->ws, 16) || (head->g && !aligned(head->g, 16)), NGNN_E_ALIGN);
-        NGNN_RETURN_IF(head->g && head->g_rows * C4 * 4 > lim, NGNN_E_RANGE);
-    }
+    const Sage2Fwd S{x, x_dev, xrow, xrow_dev, x_rows, ldx, K0, n_rows, n_rows_dev, n_edge_rows, n_edge_rows_dev, rowptr,
+                     col, col_x, reduce, wl0, bl0, wr0, ldw0, H, wl1, bl1, wr1, ldw1, F1, p_drop, seed, seed_dev, h, ldh,
+                     h_rows, h_rows_dev, agg0, ld_agg, out, ldo, head, stages, ws, ws_bytes};
+    const int rc = sage2_fwd_check(S);
+    if (rc || n_rows == 0) return rc;
     hipStream_t st = as_stream(stream);
-    char *wsb = static_cast<char *>(ws);
-    const int C0 = static_cast<int>(ceil_div(K0, 32)), NT1 = static_cast<int>(ceil_div(F1, 16));
-    float *nb = reinterpret_cast<float *>(wsb + L.nb);
-    float *z = reinterpret_cast<float *>(wsb + L.z);
-    const int64_t ldz = 16 * NT1;
-    const int64_t cap_rows = ceil_div(n_rows, 16) * 16;
-    // the saved aggregate's and nb's rows: whole edge tiles (NB: agg0 must hold
-    // ceil16(n_edge) rows when they exceed n_rows -- capped at n_rows here)
+    const Ws2 L = ws2_layout(K0, F1, n_rows);
+    float *nb = reinterpret_cast<float *>(static_cast<char *>(ws) + L.nb);
+    float *z = reinterpret_cast<float *>(static_cast<char *>(ws) + L.z);
     // (NGNN_SAGE2_PREP: accepted, nothing to do -- the kernels load their
     // weight slices themselves since ABI 13's first release)
-    const int ncu = num_cus();
+    const bool edge = S.edge_runs(), main = (stages & NGNN_SAGE2_MAIN) != 0;
     // the edge and main launches as one (k_fwd2x) when both run in this call
     // (NGNN_FWD2_FUSE=0, read once: two launches -- A/B)
-    static const bool fuse_env = [] {
-        const char *v = std::getenv("NGNN_FWD2_FUSE");
-        return !(v && v[0] == '0');
-    }();
-    bool fuse = fuse_env && (stages & NGNN_SAGE2_MAIN) && (stages & NGNN_SAGE2_EDGE) && n_edge_rows > 0 &&
-                C0 == 4 && NT1 == 3;
+    static const bool fuse_env = env_not_zero("NGNN_FWD2_FUSE");
+    bool fuse = fuse_env && edge && main;
+    int edge_dbg = 0, main_dbg = 0;
 #ifdef NGNN_FWD2_DBG_BUILD
-    if (getenv("NGNN_FWD2_DBG") || getenv("NGNN_EDGE_DBG")) fuse = false;
+    // (either variable: two launches; a known variant runs alone -- the call
+    // returns after it.  The main phase's: bit-mode dropout, plain rows, a
+    // root term)
+    const char *ed = getenv("NGNN_EDGE_DBG"), *md = getenv("NGNN_FWD2_DBG");
+    if (ed || md) fuse = false;
+    if (ed) with_const<F2_EDGE_DBG>(atoi(ed), [&](auto c) { edge_dbg = decltype(c)::value; });
+    if (md && dropout_mode(make_dropout(p_drop, seed)) == 2 && !S.indexed() && wr0)
+        with_const<F2_MAIN_DBG>(atoi(md), [&](auto c) { main_dbg = decltype(c)::value; });
 #endif
-    G2Args g{};
-    if ((stages & NGNN_SAGE2_EDGE) && n_edge_rows > 0) {
-        g.x = x;
-        g.x_dev = x_dev;
-        g.ldx = ldx;
-        g.K0 = static_cast<int>(K0);
-        g.n_rows = static_cast<int>(n_rows);
-        g.n_rows_dev = n_rows_dev;
-        g.n_edge = static_cast<int>(std::min(n_edge_rows, n_rows));
-        g.n_edge_dev = n_edge_rows_dev;
-        g.rowptr = rowptr;
-        g.col = col;
-        g.col_x = indexed ? col_x : nullptr;
-        g.x_rows = x_rows;
-        g.mean = reduce == NGNN_REDUCE_MEAN;
-        g.wl0 = wl0;
-        g.ldw0 = ldw0;
-        g.agg = agg0;
-        g.ld_agg = ld_agg;
-        g.nb = nb;
-        g.cap_rows = n_rows;  // (agg0 has n_rows rows; nb has cap_rows >= n_rows)
-        g.gz = head ? head->g : nullptr;
-        g.gz_ld = static_cast<int>(C4);
-        g.gz_rows = head ? static_cast<int>(head->g_rows) : 0;
-        g.gz_rows_dev = head ? head->g_rows_dev : nullptr;
-        g.cnt_y = head ? head->y : nullptr;
-        g.cnt_B = head ? static_cast<int>(head->B) : 0;
-        g.cnt_ignore = head ? head->ignore_index : 0;
-        g.cnt_out = head ? reinterpret_cast<float *>(static_cast<char *>(head->ws) + 4) : nullptr;
-        g.scnt_base = (head && head->g) ? head->src_count : nullptr;
-        g.scnt_stride = static_cast<int>(head ? head->g_rows : 0);
-        const int tiles = static_cast<int>(ceil_div(g.n_edge, 16));
-        const int grid = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(ncu, tiles)));
-        int rc = NGNN_E_SHAPE;
-#ifdef NGNN_FWD2_DBG_BUILD
-        if (const char *d = getenv("NGNN_EDGE_DBG")) {
-            switch (C0 == 4 ? atoi(d) : 0) {
-                case 1: return launch_edge_nb<4, 1>(g, grid, st);
-                case 2: return launch_edge_nb<4, 2>(g, grid, st);
-                case 3: return launch_edge_nb<4, 3>(g, grid, st);
-                case 4: return launch_edge_nb<4, 4>(g, grid, st);
-                case 6: return launch_edge_nb<4, 6>(g, grid, st);
-                case 7: return launch_edge_nb<4, 7>(g, grid, st);
-                case 8: return launch_edge_nb<4, 8>(g, grid, st);
-                case 16: return launch_edge_nb<4, 16>(g, grid, st);
-                case 23: return launch_edge_nb<4, 23>(g, grid, st);
-                case 24: return launch_edge_nb<4, 24>(g, grid, st);
-                default: break;
-            }
-        }
-#endif
-        if (!fuse) {
-            if (C0 == 4) rc = launch_edge_nb<4>(g, grid, st);
-            if (rc) return rc;
-        }
-    } else if ((stages & NGNN_SAGE2_EDGE) && head && head->g && head->g_rows > 0) {
+    const G2Args g = edge ? edge_args(S, nb) : G2Args{};
+    if (edge && !fuse) {
+        const int e = launch_edge(g, edge_dbg, st);
+        if (e || edge_dbg) return e;
+    } else if (!edge && (stages & NGNN_SAGE2_EDGE) && head && head->g && head->g_rows > 0) {
         // (no edge launch to zero the head's g: every row up to its static bound)
-        const hipError_t e = hipMemsetAsync(head->g, 0, static_cast<size_t>(head->g_rows * C4 * 4), st);
+        const hipError_t e = hipMemsetAsync(head->g, 0, static_cast<size_t>(head->g_rows * S.C4() * 4), st);
         if (e != hipSuccess) return static_cast<int>(e);
     }
-    if (stages & NGNN_SAGE2_MAIN) {
-        F2Args f;
-        f.x = x;
-        f.x_dev = x_dev;
-        f.ldx = ldx;
-        f.K0 = static_cast<int>(K0);
-        f.xrow = xrow;
-        f.xrow_dev = xrow_dev;
-        f.x_rows = x_rows;
-        f.n_rows = static_cast<int>(n_rows);
-        f.n_rows_dev = n_rows_dev;
-        f.n_edge = static_cast<int>(std::min(n_edge_rows, n_rows));
-        f.n_edge_dev = n_edge_rows_dev;
-        f.nb = nb;
-        f.cap_rows = cap_rows;
-        f.wr0 = wr0;
-        f.ldw0 = ldw0;
-        f.wr1 = wr1;
-        f.wl1 = wl1;
-        f.ldw1 = ldw1;
-        f.b0 = bl0;
-        f.b1 = bl1;
-        f.drop = make_dropout(p_drop, seed);
-        f.seed_dev = seed_dev;
-        f.h = h;
-        f.ldh = ldh;
-        f.h_rows = static_cast<int>(std::min(h_rows, n_rows));
-        f.h_rows_dev = h_rows_dev;
-        f.out = out;
-        f.ldo = ldo;
-        f.z = z;
-        f.ldz = ldz;
-        f.F1 = static_cast<int>(F1);
-        const int64_t tiles = ceil_div(n_rows, 16);
-        const int grid = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(ncu, tiles)));
-        const int dm = f.drop.thresh == 0 ? 0 : f.drop.thresh == 128u ? 2 : 1;
-        int rc = NGNN_E_SHAPE;
-#ifdef NGNN_FWD2_DBG_BUILD
-        if (const char *d = getenv("NGNN_FWD2_DBG")) {
-            const int v = atoi(d);
-            if (C0 == 4 && NT1 == 3 && dm == 2 && !indexed) {
-                switch (v) {
-                    case 1: return launch_fwd2<4, 3, 2, false, 1>(f, grid, st);
-                    case 2: return launch_fwd2<4, 3, 2, false, 2>(f, grid, st);
-                    case 3: return launch_fwd2<4, 3, 2, false, 3>(f, grid, st);
-                    case 4: return launch_fwd2<4, 3, 2, false, 4>(f, grid, st);
-                    case 8: return launch_fwd2<4, 3, 2, false, 8>(f, grid, st);
-                    case 15: return launch_fwd2<4, 3, 2, false, 15>(f, grid, st);
-                    case 16: return launch_fwd2<4, 3, 2, false, 16>(f, grid, st);
-                    case 32: return launch_fwd2<4, 3, 2, false, 32>(f, grid, st);
-                    case 64: return launch_fwd2<4, 3, 2, false, 64>(f, grid, st);
-                    default: break;
-                }
-            }
-        }
-#endif
-        // (K0 <= 112: the 16-deep tail chunk; NGNN_FWD2_T16=0 forces 4 x 32 -- A/B)
-        static const bool t16_ok = [] {
-            const char *v = std::getenv("NGNN_FWD2_T16");
-            return !(v && v[0] == '0');
-        }();
-        const bool t16 = t16_ok && K0 <= 112;
-        auto go = [&](auto xr_c) {
-            constexpr bool XRv = decltype(xr_c)::value;
-            if (!wr0) {  // (root-free: no x, so no T16 form; never indexed)
-                if (fuse)
-                    return dm == 2   ? launch_fwd2x<4, 3, 2, false, false, false>(g, f, grid, st)
-                           : dm == 1 ? launch_fwd2x<4, 3, 1, false, false, false>(g, f, grid, st)
-                                     : launch_fwd2x<4, 3, 0, false, false, false>(g, f, grid, st);
-                return dm == 2   ? launch_fwd2<4, 3, 2, false, 0, false, false>(f, grid, st)
-                       : dm == 1 ? launch_fwd2<4, 3, 1, false, 0, false, false>(f, grid, st)
-                                 : launch_fwd2<4, 3, 0, false, 0, false, false>(f, grid, st);
-            }
-            if (fuse) {
-                if (t16)
-                    return dm == 2   ? launch_fwd2x<4, 3, 2, XRv, true>(g, f, grid, st)
-                           : dm == 1 ? launch_fwd2x<4, 3, 1, XRv, true>(g, f, grid, st)
-                                     : launch_fwd2x<4, 3, 0, XRv, true>(g, f, grid, st);
-                return dm == 2   ? launch_fwd2x<4, 3, 2, XRv>(g, f, grid, st)
-                       : dm == 1 ? launch_fwd2x<4, 3, 1, XRv>(g, f, grid, st)
-                                 : launch_fwd2x<4, 3, 0, XRv>(g, f, grid, st);
-            }
-            if (t16)
-                return dm == 2   ? launch_fwd2<4, 3, 2, XRv, 0, true>(f, grid, st)
-                       : dm == 1 ? launch_fwd2<4, 3, 1, XRv, 0, true>(f, grid, st)
-                                 : launch_fwd2<4, 3, 0, XRv, 0, true>(f, grid, st);
-            return dm == 2   ? launch_fwd2<4, 3, 2, XRv>(f, grid, st)
-                   : dm == 1 ? launch_fwd2<4, 3, 1, XRv>(f, grid, st)
-                             : launch_fwd2<4, 3, 0, XRv>(f, grid, st);
-        };
-        if (C0 == 4 && NT1 == 3) rc = indexed ? go(std::true_type{}) : go(std::false_type{});
-        if (rc) return rc;
+    if (main) {
+        const int e = launch_main(S, g, main_args(S, nb, z), fuse, main_dbg, st);
+        if (e || main_dbg) return e;
     }
     if (!(stages & NGNN_SAGE2_NARROW)) return NGNN_OK;
     NarrowHead nh{};
-    if (head) {
-        nh.y = head->y;
-        nh.B = static_cast<int>(head->B);
-        nh.ignore = head->ignore_index;
-        nh.loss = head->loss;
-        nh.count = head->count;
-        nh.dy = head->dy;
-        nh.ldd = head->ldd;
-        nh.g = head->g;
-        nh.ldg = static_cast<int>(C4);
-        nh.ticket = static_cast<uint32_t *>(head->ws);
-        nh.part = reinterpret_cast<float *>(static_cast<char *>(head->ws) + 256);
-        // the count from this call's edge launch (ws + 4), else counted there
-        nh.cnt_in = ((stages & NGNN_SAGE2_EDGE) && n_edge_rows > 0)
-                        ? reinterpret_cast<const float *>(static_cast<char *>(head->ws) + 4)
-                        : nullptr;
-        // the seed-edge counts only when this call's edge launch counted them
-        if ((stages & NGNN_SAGE2_EDGE) && n_edge_rows > 0 && head->g) {
-            nh.scnt_base = head->src_count;
-            nh.scnt_stride = static_cast<int>(head->g_rows);
-        }
-#ifdef NGNN_FWD2_DBG_BUILD
-        if (const char *d = getenv("NGNN_HEAD_DBG")) {
-            nh.dbg = atoi(d);
-            if (nh.dbg & 16) nh.cnt_in = reinterpret_cast<const float *>(static_cast<char *>(head->ws) + 4);
-        }
-#endif
-    }
-    return narrow_agg_launch(z, ldz, F1, rowptr, col, n_rows, n_rows_dev, n_edge_rows, n_edge_rows_dev, reduce,
+    if (head) nh = narrow_head(S);
+    return narrow_agg_launch(z, S.ldz(), F1, rowptr, col, n_rows, n_rows_dev, n_edge_rows, n_edge_rows_dev, reduce,
                              out, ldo, st, head ? &nh : nullptr);
 }

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstdlib>
 #include <type_traits>
 
 #include "ngnn.h"
@@ -32,7 +33,24 @@ inline bool aligned(const void *p, size_t a) {
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// Largest whole-buffer range in bytes: the kernels address a whole operand
+// through one buffer resource with unsigned 32-bit offsets, and offsets from
+// 0xF0000000 up mean "out of range" (kOOB) -- every such operand stays 4 KiB
+// under that.
+constexpr int64_t kRangeMax = 0xF0000000ll - 4096;
+
 int num_cus();  // compute units of the current device (cached; ngnn_sage_rt.hip)
+
+// Environment switches, for `static const` initialisers (read once per
+// process): on unless the variable starts with '0'; an int, dflt when unset.
+inline bool env_not_zero(const char *name) {
+    const char *e = std::getenv(name);
+    return !(e && e[0] == '0');
+}
+inline int env_int(const char *name, int dflt) {
+    const char *e = std::getenv(name);
+    return e ? std::atoi(e) : dflt;
+}
 
 // Runtime int -> template argument: f(std::integral_constant<int, V>{}) for
 // the first V of the list equal to v; the last V is the default, as a

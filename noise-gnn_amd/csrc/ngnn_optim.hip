@@ -238,10 +238,7 @@ extern "C" int ngnn_adam_step(int n_tensors, float *const *params, const float *
         // at most 2 workgroups per CU: the rest is the grid-stride loop (and at
         // most 32 x kAdamGroups -- the ticket's groups)
         // (NGNN_ADAM_WG_PER_CU, read once: the per-CU cap -- A/B)
-        static const int wg_cu = [] {
-            const char *e = std::getenv("NGNN_ADAM_WG_PER_CU");
-            return e ? std::max(1, std::atoi(e)) : 2;
-        }();
+        static const int wg_cu = std::max(1, env_int("NGNN_ADAM_WG_PER_CU", 2));
         const unsigned grid = static_cast<unsigned>(std::min<int64_t>(std::min<int64_t>(T.boff[T.n], wg_cu * num_cus()),
                                                                       32 * kAdamGroups));
         hipLaunchKernelGGL(k_adam, dim3(grid), dim3(256), 0, st, T, step, ticket, lr, beta1, beta2,

@@ -1259,10 +1259,7 @@ void launch_wgrad_x3(const WgradArgs &a, int S, int gy) {
     // (NGNN_WGRAD_NFW=2, read once: two Fo tiles per wave -- half the
     // h / agg re-reads, but the bf16-mask form spills: 429 vs 250 us on
     // config #3's layer 0, A/B only)
-    static const int nfw_max = [] {
-        const char *e = std::getenv("NGNN_WGRAD_NFW");
-        return e ? std::max(1, std::min(2, std::atoi(e))) : 1;
-    }();
+    static const int nfw_max = std::max(1, std::min(2, env_int("NGNN_WGRAD_NFW", 1)));
     const int nfw = hb && a.Fo >= 128 ? nfw_max : 1;
     const size_t lds = (static_cast<size_t>(3) * WG_BM * (WG_NC * nfw + 16) + (hb ? 1 : 3) * WG_BM * X3H +
                         static_cast<size_t>(3) * WG_BM * X3H) * 2;
@@ -1341,10 +1338,7 @@ extern "C" int ngnn_sage_wgrad(const float *dy, int64_t ldy, const float *y, int
     const dim3 grid(S, static_cast<unsigned>(gy), static_cast<unsigned>(gz));
     const int NT = static_cast<int>(ceil_div(std::min<int64_t>(Fo, WG_NC), 16));
     // (NGNN_WGRAD_X3=0, read once: the exact-f32 MFMA kernel for every shape -- A/B)
-    static const bool x3_on = [] {
-        const char *e = std::getenv("NGNN_WGRAD_X3");
-        return !(e && e[0] == '0');
-    }();
+    static const bool x3_on = env_not_zero("NGNN_WGRAD_X3");
     // (fp32 h / agg rows at 4-B alignment, K % 4 != 0 -- Amazon-Computers' K =
     // 767: the X3 kernel's 16-B loads read past K into the next row, and
     // store_parts zeroes those columns)
@@ -1465,10 +1459,7 @@ extern "C" int ngnn_sage_dgrad_fused(const float *dy, int64_t ldy, const float *
     // layer: 40 KB) is as cheap from L2, and without the LDS copy the grid is
     // not held to one workgroup per CU (NGNN_DGRAD_LDSW=1 / 0, read once:
     // always / never -- A/B)
-    static const int ldsw_env = [] {
-        const char *e = std::getenv("NGNN_DGRAD_LDSW");
-        return e ? std::atoi(e) : -1;
-    }();
+    static const int ldsw_env = env_int("NGNN_DGRAD_LDSW", -1);
     const bool lds_w = ((Fo * K) % 4 == 0) && aligned(wl, 16) && aligned(wr, 16) && fused_w_fits_lds(Fo, K) &&
                        (ldsw_env == 1 || (ldsw_env < 0 && Fo >= 32));
     const unsigned g = static_cast<unsigned>(

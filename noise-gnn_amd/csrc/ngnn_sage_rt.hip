@@ -696,10 +696,7 @@ int launch_slice(RtArgs &a, const RtPlan &p, const RtSlice &s, int reduce, int n
     // layers with edge tiles (k_sage_rt edge tiles, then k_root -- measured
     // slower on products layer 0: the edge tiles alone then hold the GPU
     // ~48 us, in one launch they overlap the root tiles); 0 never
-    static const int policy = [] {
-        const char *e = std::getenv("NGNN_ROOT");
-        return e ? std::atoi(e) : 1;
-    }();
+    static const int policy = env_int("NGNN_ROOT", 1);
     const bool want_root = policy == 2 || (policy == 1 && !a.wl);
     if (form && want_root && launch_root(a, s.NTW, form, vec, st, true) == NGNN_OK) {
         if (a.wl) {
@@ -844,10 +841,7 @@ extern "C" int ngnn_sage_fwd_raw(const float *x, const float *const *x_dev, cons
     const size_t head = want_narrow ? static_cast<size_t>(n_rows) * ldz * sizeof(float)
                                     : ngnn_pack_weight_bytes(Fo, K) + wl_b16_bytes(Fo, K);
     // (NGNN_IMG=0, read once: every workgroup builds its image -- A/B only)
-    static const bool img_on = [] {
-        const char *e = std::getenv("NGNN_IMG");
-        return !e || std::atoi(e) != 0;
-    }();
+    static const bool img_on = env_int("NGNN_IMG", 1) != 0;
     if (img_on && ws && aligned(ws, 16) && ws_bytes >= head + kImgWsBytes + 16) {
         const uintptr_t e = (reinterpret_cast<uintptr_t>(ws) + ws_bytes - kImgWsBytes) & ~uintptr_t(15);
         L.img_ws = reinterpret_cast<void *>(e);
@@ -880,10 +874,7 @@ extern "C" int ngnn_sage_fwd_raw(const float *x, const float *const *x_dev, cons
     // NGNN_AGGPRE (read once; A/B): 1 -- mean / sum layers too (layer 0 of
     // products: its 16.2 k rows with in-edges gathered at full occupancy
     // instead of inside the row-tile kernel, one wave per 16-row tile)
-    static const int aggpre_all = [] {
-        const char *e = std::getenv("NGNN_AGGPRE");
-        return e ? std::atoi(e) : 0;
-    }();
+    static const int aggpre_all = env_int("NGNN_AGGPRE", 0);
     L.agg_pre = (reduce == NGNN_REDUCE_MAX ? K >= 256 : aggpre_all == 1) && wl && agg_out &&
                 (x || x_dev) && !xrow && !xrow_dev && !L.x_bf16 && ld_agg % 4 == 0 &&
                 aligned(agg_out, 16);

@@ -205,7 +205,6 @@ __device__ __forceinline__ v4f and_mask(v4f v, int m) {
 // resource of the gather source is capped below it (host check), every other
 // resource covers one 16-row tile; offsets are unsigned 32-bit
 constexpr int kOOB = static_cast<int>(0xF0000000u);
-constexpr int64_t kRangeMax = 0xF0000000ll - 4096;  // largest whole-buffer range
 
 // resource over tile t's rows of a row-major [n_rows, ld] matrix (64-bit
 // base per tile: no whole-buffer size limit).  It covers the 16 rows plus

@@ -860,20 +860,15 @@ unsigned wide_agg_blocks(int64_t n_edge) {
 // empty / null.
 int launch_wide_agg(const LayerFwd &L, int64_t n_edge, unsigned grid, float *agg, int64_t lda, int round16, int *ea,
                     const WidePrep &prep, hipStream_t st) {
-    auto launch_agg = [&](auto red_c, auto nc_c) {
-        hipLaunchKernelGGL((k_wide_agg<decltype(red_c)::value, decltype(nc_c)::value>), dim3(grid), dim3(256), 0, st,
-                           L.x, L.ldx, static_cast<int>(L.K), L.rowptr, L.col, static_cast<int>(n_edge),
-                           L.n_rows_dev, L.n_edge_rows_dev, agg, lda, static_cast<int>(L.n_rows), round16, L.x_dev,
-                           ea, prep);
-    };
-    auto by_nc = [&](auto red_c) {
-        if (L.K <= 256) launch_agg(red_c, std::integral_constant<int, 4>{});
-        else if (L.K <= 512) launch_agg(red_c, std::integral_constant<int, 8>{});
-        else launch_agg(red_c, std::integral_constant<int, 12>{});  // (> 768: passes of 768)
-    };
-    if (L.reduce == NGNN_REDUCE_MEAN) by_nc(std::integral_constant<int, NGNN_REDUCE_MEAN>{});
-    else if (L.reduce == NGNN_REDUCE_SUM) by_nc(std::integral_constant<int, NGNN_REDUCE_SUM>{});
-    else by_nc(std::integral_constant<int, NGNN_REDUCE_MAX>{});
+    const int nc = L.K <= 256 ? 4 : L.K <= 512 ? 8 : 12;  // (> 768: passes of 768)
+    with_const<NGNN_REDUCE_MEAN, NGNN_REDUCE_SUM, NGNN_REDUCE_MAX>(L.reduce, [&](auto red_c) {
+        with_const<4, 8, 12>(nc, [&](auto nc_c) {
+            hipLaunchKernelGGL((k_wide_agg<decltype(red_c)::value, decltype(nc_c)::value>), dim3(grid), dim3(256), 0,
+                               st, L.x, L.ldx, static_cast<int>(L.K), L.rowptr, L.col, static_cast<int>(n_edge),
+                               L.n_rows_dev, L.n_edge_rows_dev, agg, lda, static_cast<int>(L.n_rows), round16,
+                               L.x_dev, ea, prep);
+        });
+    });
     return launch_status();
 }
 
@@ -890,10 +885,7 @@ int sage_fwd_wide(const LayerFwd &L, hipStream_t st) {
     // offsets, and room for the 2-part image + the row / column exponents at
     // the workspace tail -- decided first: the aggregation writes the
     // neighbour rows' exponents
-    static const bool h2_on = [] {
-        const char *e = std::getenv("NGNN_WIDE_H2");
-        return !(e && e[0] == '0');
-    }();
+    static const bool h2_on = env_not_zero("NGNN_WIDE_H2");
     const bool has_agg = wl && n_edge > 0;
     const int64_t lda_eff = L.agg_out ? L.ld_agg : K;
     const bool fits = n_rows * L.ldx * 4 < 0x7FFF0000ll && (!has_agg || n_edge * lda_eff * 4 < 0x7FFF0000ll);
@@ -960,10 +952,7 @@ int sage_fwd_wide(const LayerFwd &L, hipStream_t st) {
     a.seed_dev = L.seed_dev;
     a.n_ct = static_cast<int>(ceil_div(Fo, WBN));
     // (NGNN_WIDE_XCD=0, read once: k_wide_h2's plain tile order -- A/B)
-    static const bool xcd_on = [] {
-        const char *e = std::getenv("NGNN_WIDE_XCD");
-        return !(e && e[0] == '0');
-    }();
+    static const bool xcd_on = env_not_zero("NGNN_WIDE_XCD");
     a.xcd = 0;
     const int64_t tiles = ceil_div(n_rows, WBM) * a.n_ct;
     NGNN_RETURN_IF(tiles > INT32_MAX, NGNN_E_RANGE);
@@ -973,10 +962,7 @@ int sage_fwd_wide(const LayerFwd &L, hipStream_t st) {
     const bool vout = (L.ldo % 4 == 0) && aligned(L.out, 16);
     // the split-bf16 form (not under NGNN_MATH_EXACT_F32): its weight image at
     // the workspace's tail (NGNN_WIDE_X3=0, read once: the exact f32 form -- A/B)
-    static const bool x3_on = [] {
-        const char *e = std::getenv("NGNN_WIDE_X3");
-        return !(e && e[0] == '0');
-    }();
+    static const bool x3_on = env_not_zero("NGNN_WIDE_X3");
     const size_t ib = wide_wimg_bytes(K, Fo);
     {
         if (use_h2) {
@@ -988,29 +974,22 @@ int sage_fwd_wide(const LayerFwd &L, hipStream_t st) {
                 if (rc) return rc;
             }
             // (NGNN_WIDE_BM=128, read once: the eight-wave 128-row tile -- A/B)
-            static const int bm = [] {
-                const char *e = std::getenv("NGNN_WIDE_BM");
-                return (e && std::atoi(e) == 128) ? 128 : 64;
-            }();
-            static bool attr_set[2][2] = {};
-            auto go = [&](auto kern, int bm_c) {
-                const size_t lds = static_cast<size_t>(2) * (2 * bm_c * WKC + 2 * WBN * WKC) * 2;
-                bool &set = attr_set[vout][bm_c == 128];
-                if (!set) {
-                    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                                             hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                             static_cast<int>(lds));
-                    if (e != hipSuccess) return static_cast<int>(e);
-                    set = true;
-                }
-                const int64_t t2 = ceil_div(n_rows, bm_c) * a.n_ct;
-                const int64_t g2 = std::max<int64_t>(8, std::min<int64_t>(ceil_div(t2, 8) * 8, (128 / bm_c) * num_cus()));
-                a.xcd = (xcd_on && g2 % 8 == 0) ? 1 : 0;  // (the XCD order needs whole groups of 8)
-                hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(g2)), dim3(bm_c * 4), lds, st, a, img, Kp, ew, ex, ea);
-                return launch_status();
-            };
-            if (bm == 128) return vout ? go(k_wide_h2<true, 128>, 128) : go(k_wide_h2<false, 128>, 128);
-            return vout ? go(k_wide_h2<true, 64>, 64) : go(k_wide_h2<false, 64>, 64);
+            static const int bm = env_int("NGNN_WIDE_BM", 64);
+            with_const<128, 64>(bm, [&](auto bm_k) {
+                with_const<1, 0>(vout, [&](auto v_c) {
+                    constexpr int bm_c = decltype(bm_k)::value;
+                    constexpr auto kern = k_wide_h2<decltype(v_c)::value != 0, bm_c>;
+                    const size_t lds = static_cast<size_t>(2) * (2 * bm_c * WKC + 2 * WBN * WKC) * 2;
+                    max_dynamic_lds_once<kern>(lds);
+                    const int64_t t2 = ceil_div(n_rows, bm_c) * a.n_ct;
+                    const int64_t g2 =
+                        std::max<int64_t>(8, std::min<int64_t>(ceil_div(t2, 8) * 8, (128 / bm_c) * num_cus()));
+                    a.xcd = (xcd_on && g2 % 8 == 0) ? 1 : 0;  // (the XCD order needs whole groups of 8)
+                    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(g2)), dim3(bm_c * 4), lds, st, a, img, Kp, ew,
+                                       ex, ea);
+                });
+            });
+            return launch_status();
         }
     }
     if (!L.exact && x3_on && fits && ws && ws_bytes >= head + ib + 256) {
@@ -1022,18 +1001,11 @@ int sage_fwd_wide(const LayerFwd &L, hipStream_t st) {
         int rc = launch_status();
         if (rc) return rc;
         const size_t lds = static_cast<size_t>(2) * XW_STAGE * 2;
-        auto go = [&](auto v_c) {
-            auto fn = k_wide_x3<decltype(v_c)::value>;
-            static bool attr = false;  // benign race: idempotent
-            if (!attr) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(fn),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-                attr = true;
-            }
+        with_const<1, 0>(vout, [&](auto v_c) {
+            constexpr auto fn = k_wide_x3<decltype(v_c)::value != 0>;
+            max_dynamic_lds_once<fn>(lds);
             hipLaunchKernelGGL(fn, dim3(static_cast<unsigned>(grid)), dim3(256), lds, st, a, img, Kp);
-        };
-        if (vout) go(std::true_type{});
-        else go(std::false_type{});
+        });
         return launch_status();
     }
     if (vout)

@@ -486,6 +486,14 @@ def _absent_none(params, grads):
     return [None if q is None else g for q, g in zip(params, grads)]
 
 
+def _shared_ld(wl, wr):
+    """A layer's (W_l, W_r) as the two-layer entries take them: unit-stride
+    rows and one row stride for both (ldw0 / ldw1), else contiguous copies."""
+    if wl.stride(1) != 1 or wr.stride(0) != wl.stride(0) or wr.stride(1) != 1:
+        return wl.contiguous(), wr.contiguous()
+    return wl, wr
+
+
 def sage2_forward(x, block: Block, reduce: str, params, p_drop: float, seed: int, seed_dev,
                   stages: int | None = None, bufs=None, head: "HeadResult | None" = None,
                   root0: bool = True):
@@ -500,10 +508,8 @@ def sage2_forward(x, block: Block, reduce: str, params, p_drop: float, seed: int
     fused x[n_id] gather, which keeps the zero matrix."""
     # (pointers and strides only: no detach -- nothing here records autograd)
     wl0, bl0, wr0, wl1, bl1, wr1 = params
-    if wl0.stride(1) != 1 or wr0.stride(0) != wl0.stride(0) or wr0.stride(1) != 1:
-        wl0, wr0 = wl0.contiguous(), wr0.contiguous()
-    if wl1.stride(1) != 1 or wr1.stride(0) != wl1.stride(0) or wr1.stride(1) != 1:
-        wl1, wr1 = wl1.contiguous(), wr1.contiguous()
+    wl0, wr0 = _shared_ld(wl0, wr0)
+    wl1, wr1 = _shared_ld(wl1, wr1)
     bl0, bl1 = bl0.contiguous(), bl1.contiguous()
     N, K0 = x.shape
     H, F1 = wl0.shape[0], wl1.shape[0]
@@ -723,8 +729,7 @@ def sage2_backward(dy, block: Block, reduce: str, acts, agg0, params, p_drop: fl
     N, K0 = x.shape[0], wl0.shape[1]
     F1 = wl1.shape[0]
     w1l, w1r = wl1.detach(), wr1.detach()
-    if w1l.stride(1) != 1 or w1r.stride(0) != w1l.stride(0) or w1r.stride(1) != 1:
-        w1l, w1r = w1l.contiguous(), w1r.contiguous()
+    w1l, w1r = _shared_ld(w1l, w1r)
     grads = [(g.view(q.shape) if g is not None else torch.empty_like(q))
              for g, q in zip(views, (wl0, bl0, wr0, wl1, bl1, wr1))]
     if root_free:  # (ABI 18: a SimpleGCN stack -- no x reads, no W_r gradients)
