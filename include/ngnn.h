@@ -1042,6 +1042,80 @@ int ngnn_contrast_bwd(const float *h, int64_t ldh, const float *hp, int64_t ldp,
                       const void *ws, const float *grad_scale, float *dh, int64_t lddh, float *dhp,
                       int64_t lddp, float *dhn, int64_t lddn, void *stream);
 
+/* ------------------- neighbourhood uncertainty and the consistency loss
+ * Added within ABI 22 (new entries only: nothing existing changed, so the
+ * version did not move).
+ *
+ * ngnn_nbr_uncertainty: get_uncertainty_batch(edge_index, y_pure,
+ * nbr_classes, device, epsilon) of src/utils/losses.py:185-204 on the rows
+ * [0, R) of a block, R <= n_rows.  logp: float [n_rows, C] log-probabilities
+ * (row stride ld); rowptr int32 [n_rows + 1] / col int32 [E]: the edges
+ * grouped by SOURCE, rowptr by edge_index[0] and col = edge_index[1] (the
+ * reference's A = coo(row = edge_index[0], col = edge_index[1]), A @ p: the
+ * transpose of what SAGEConv aggregates).  With p = exp(logp):
+ *   s_i   = sum over list(i) of p[col[e]]       (duplicates and self-loops count)
+ *   ptc_i = s_i / (deg_i + epsilon)             (deg_i = the list's length)
+ *   h_i   = -sum_k ptc_ik log2(ptc_ik + 1e-5)
+ *   w[i]  = exp(-h_i / log2(nbr_classes))       (an empty list: exactly 1)
+ * One wave per row, lanes over the classes (a chunk loop for C > 64), the
+ * list summed in list order in fp32 (groups of four, a Kahan compensation
+ * across them: a hub's thousands of terms cost no accuracy), the entropy
+ * reduced with wave shuffles:
+ * no atomics, no workspace, no host wait, bitwise reproducible for a given
+ * CSR; a wave runs as long as its list.  Nothing past w[R) is written,
+ * columns [C, ld) are never read.  A col entry outside [0, n_rows) reads
+ * nothing and makes its row's w NaN.  R == 0: NGNN_OK, nothing read.  Before
+ * any launch: a negative size, R > n_rows, nbr_classes < 2 (the reference
+ * divides by log2(1) = 0), a NULL logp / rowptr / w with rows to write (col
+ * may be NULL for a CSR without edges): NGNN_E_ARG; ld < C: NGNN_E_SHAPE;
+ * n_rows or R >= 2^31, C > 65535: NGNN_E_RANGE.
+ * Replaces edge_index.cpu(), a scipy COO build, a sparse tensor upload,
+ * torch.sparse.mm, a sparse row sum and about ten elementwise launches
+ * [ext: torch, scipy]. */
+int ngnn_nbr_uncertainty(const float *logp, int64_t ld, int64_t n_rows, int64_t C,
+                         const int32_t *rowptr, const int32_t *col, int64_t R, int64_t nbr_classes,
+                         float epsilon, float *w, void *stream);
+
+/* fix_cr(y_pure, y_noisy, ind_noisy, batch_size, name, T, p_cutoff,
+ * use_hard_labels, w) of src/utils/losses.py:206-246 on the rows [0, B) of
+ * the log-probabilities lp_pure, lp_noisy (float, C columns, row strides ldp,
+ * ldn).  Per row r: pp = exp(lp_pure[r]), pn = exp(lp_noisy[r]),
+ * s = softmax(pn) (the reference feeds the probabilities pn to cross_entropy
+ * as logits), m_r = [max_k pp_k >= p_cutoff], k* the FIRST index of that
+ * maximum (torch.max's tie rule; a NaN is the maximum and masks the row),
+ * w_r = w[r] (1 when w is NULL), c_r = g m_r w_r / B.
+ *   mode 0 (name 'ce', hard labels): l_r = logsumexp(pn) - pn[k*]
+ *     d lp_noisy[r,k] = c_r (s_k - [k == k*]) pn_k;  d lp_pure = 0
+ *   mode 1 (name 'ce', soft labels): l_r = -sum_k pp_k log_softmax(pn)_k
+ *     d lp_pure [r,k] = -c_r pp_k log_softmax(pn)_k   (pp is not detached)
+ *     d lp_noisy[r,k] =  c_r (s_k sum_j pp_j - pp_k) pn_k
+ *   modes 0, 1: loss = (1/B) sum_r w_r (m_r l_r) -- the mean over all B rows,
+ *     the mask a factor: a NaN row term makes the loss NaN even at m_r = 0
+ *   mode 2 (name 'l2'): loss = (1/(B C)) sum_rk (lp_noisy - lp_pure)^2,
+ *     d lp_noisy = 2 g (lp_noisy - lp_pure) / (B C) = -d lp_pure;
+ *     w and p_cutoff are not read
+ * ngnn_fix_cr_fwd writes *loss and, for each of d_pure / d_noisy that is not
+ * NULL, its gradient rows [0, B) at unit scale (g = 1); ngnn_fix_cr_bwd
+ * recomputes from the inputs (no state between the calls) and writes them
+ * for the device scalar *grad_scale (either may be NULL; in mode 0 a given
+ * d_pure is written as zeros).  Rows >= B and columns >= C are never read or
+ * written.  One wave per row, the row terms added in a fixed order by a
+ * second launch: deterministic.  ws: ngnn_fix_cr_workspace_bytes(B), 16-B
+ * aligned, free after the forward.  Before any launch: a NULL lp_pure /
+ * lp_noisy / loss / ws (fwd) / grad_scale (bwd), B or C <= 0, a mode outside
+ * {0, 1, 2}: NGNN_E_ARG; ldp, ldn or a given gradient's stride < C:
+ * NGNN_E_SHAPE; B >= 2^31 or C > 65535: NGNN_E_RANGE; ws too small or
+ * misaligned: NGNN_E_WORKSPACE.
+ * Replaces two slices, two exp, max, ge, cross_entropy (or log_softmax, mul,
+ * sum), two mul, mean and their autograd [ext: torch]. */
+size_t ngnn_fix_cr_workspace_bytes(int64_t B);
+int ngnn_fix_cr_fwd(const float *lp_pure, int64_t ldp, const float *lp_noisy, int64_t ldn, int64_t B,
+                    int64_t C, int mode, float p_cutoff, const float *w, float *loss, float *d_pure,
+                    int64_t lddp, float *d_noisy, int64_t lddn, void *ws, size_t ws_bytes, void *stream);
+int ngnn_fix_cr_bwd(const float *lp_pure, int64_t ldp, const float *lp_noisy, int64_t ldn, int64_t B,
+                    int64_t C, int mode, float p_cutoff, const float *w, const float *grad_scale,
+                    float *d_pure, int64_t lddp, float *d_noisy, int64_t lddn, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

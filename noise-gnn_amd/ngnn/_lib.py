@@ -143,6 +143,13 @@ SIGNATURES = {
     "ngnn_contrast_fwd": (_int, [_p, _i64, _p, _i64, _p, _i64, _i64, _i64, _p, _i64, _p, _p, _p, _sz, _p]),
     "ngnn_contrast_bwd": (_int, [_p, _i64, _p, _i64, _p, _i64, _i64, _i64, _p, _i64, _p, _p, _p, _i64, _p,
                                  _i64, _p, _i64, _p]),
+    # (added within ABI 22: neighbourhood uncertainty and the consistency loss)
+    "ngnn_nbr_uncertainty": (_int, [_p, _i64, _i64, _i64, _p, _p, _i64, _i64, ctypes.c_float, _p, _p]),
+    "ngnn_fix_cr_workspace_bytes": (_sz, [_i64]),
+    "ngnn_fix_cr_fwd": (_int, [_p, _i64, _p, _i64, _i64, _i64, _int, ctypes.c_float, _p, _p, _p, _i64, _p,
+                               _i64, _p, _sz, _p]),
+    "ngnn_fix_cr_bwd": (_int, [_p, _i64, _p, _i64, _i64, _i64, _int, ctypes.c_float, _p, _p, _p, _i64, _p,
+                               _i64, _p]),
 }
 
 _lib = None

@@ -20,7 +20,10 @@ the argsorts and the exchange on the device) and ``backward_correction``
 the correction matrix kept on the device), and so does the contrastive term
 of the reference's train_ct step, ``contrastive_loss`` (ngnn_contrast_*:
 ``Discriminator_innerprod`` + ``BCEExeprtLoss`` on the rows an index tensor
-names, one launch pair each way).
+names, one launch pair each way), and the uncertainty-weighted consistency
+term of its train_ct step, ``get_uncertainty_batch`` and ``fix_cr``
+(ngnn_nbr_uncertainty: one launch on the block's by-source CSR;
+ngnn_fix_cr_*: one launch pair each way).
 """
 from __future__ import annotations
 
@@ -773,3 +776,156 @@ class BCEExeprtLoss(torch.nn.Module):
         pos = torch.squeeze(logits_p1)
         neg = torch.squeeze(logits_n)
         return torch.nn.functional.softplus(-pos).mean() + torch.nn.functional.softplus(neg).mean()
+
+
+# ---------------------------------------------------------------------------
+# Uncertainty-weighted consistency (get_uncertainty_batch, fix_cr:
+# src/utils/losses.py:185-246; pipeline_ctp.py:127-135)
+
+def get_uncertainty_batch(edge_index, y_pure: torch.Tensor, nbr_classes: int, device=None,
+                          epsilon: float = 1e-16, rows: int | None = None) -> torch.Tensor:
+    """Drop-in for the reference's ``get_uncertainty_batch(edge_index, y_pure,
+    nbr_classes, device, epsilon)`` (losses.py:185-204): per node the entropy
+    weight ``exp(-H(mean of exp(y_pure) over its out-neighbours) /
+    log2(nbr_classes))``, grouped by ``edge_index[0]`` as the reference's
+    ``A @ p`` -- ONE launch (``ngnn_nbr_uncertainty``) on the by-source CSR the
+    model's backward builds anyway (``get_block(...).transposed()``), instead
+    of ``edge_index.cpu()``, a scipy COO build, a sparse upload,
+    ``torch.sparse.mm`` and a dozen elementwise launches.  No host wait, no
+    atomics: bitwise reproducible for a given block.
+
+    ``edge_index``: a ``[2, E]`` device tensor or a ``Block``.  ``rows``
+    (extension): only ``w[:rows]`` is computed and returned -- all the
+    pipeline reads (``w[:batch_size]``).  The result never carries a gradient
+    (the reference is called under ``no_grad``).  ``nbr_classes < 2`` raises
+    ``ValueError`` (the reference divides by ``log2(1) = 0``).  ``device`` is
+    accepted and unused.  fp32, GPU only."""
+    from .block import get_block
+    if not isinstance(y_pure, torch.Tensor) or not y_pure.is_cuda:
+        raise RuntimeError("ngnn.losses.get_uncertainty_batch: GPU only (no CPU fallback)")
+    if isinstance(edge_index, torch.Tensor) and not edge_index.is_cuda:
+        raise RuntimeError("ngnn.losses.get_uncertainty_batch: GPU only (no CPU fallback): edge_index")
+    if int(nbr_classes) < 2:
+        raise ValueError(f"get_uncertainty_batch: nbr_classes {nbr_classes} < 2")
+    if y_pure.dim() != 2 or y_pure.dtype != torch.float32:
+        raise ValueError("y_pure must be a 2-D float32 tensor")
+    y = y_pure.detach()
+    if y.size(1) and y.stride(1) != 1:
+        y = y.contiguous()
+    N, C = y.shape
+    blk = get_block(edge_index, N)
+    if blk.n_src != N or blk.n_dst != N:
+        raise ValueError(f"the block has {blk.n_src} x {blk.n_dst} nodes, y_pure {N} rows")
+    R = N if rows is None else int(rows)
+    if not 0 <= R <= N:
+        raise ValueError(f"rows {rows} outside [0, {N}]")
+    w = torch.empty(R, dtype=torch.float32, device=y.device)
+    if R:
+        csr = blk.transposed()
+        _lib.check(_lib.load().ngnn_nbr_uncertainty(
+            _lib.ptr(y), y.stride(0) if N > 1 else max(C, 1), N, C, _lib.ptr(csr.rowptr), _lib.ptr(csr.col),
+            R, int(nbr_classes), float(epsilon), _lib.ptr(w), _lib.stream_handle(y.device)),
+            "ngnn_nbr_uncertainty")
+    return w
+
+
+def _ld(t: torch.Tensor) -> int:
+    """Row stride of a [B, C] view (a single row's stride is arbitrary)."""
+    return t.stride(0) if t.size(0) > 1 else max(t.stride(0), t.size(1))
+
+
+_FIX_CR_MODES = {("ce", True): 0, ("ce", False): 1, ("l2", True): 2, ("l2", False): 2}
+
+
+class _FixCR(torch.autograd.Function):
+    """ngnn_fix_cr_fwd / _bwd on the B rows it is handed (the caller's
+    ``y[:B]`` views: torch's slice backward zero-fills the rows past B).  As
+    _BCLoss, the forward writes the unit-scale gradient rows; the backward
+    hands them over for the training step's unit gradient and otherwise
+    rewrites them for the incoming device scalar (one launch, recomputed from
+    the inputs)."""
+
+    @staticmethod
+    def forward(ctx, yp, yn, w, mode: int, p_cutoff: float):
+        B, C = yp.shape
+        dev = yp.device
+        lib = _lib.load()
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        ws = torch.empty(lib.ngnn_fix_cr_workspace_bytes(B), dtype=torch.uint8, device=dev)
+        # hard labels: nothing flows into y_pure (its gradient is None)
+        dp = torch.empty(B, C, dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] and mode else None
+        dn = torch.empty(B, C, dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
+        _lib.check(lib.ngnn_fix_cr_fwd(
+            _lib.ptr(yp), _ld(yp), _lib.ptr(yn), _ld(yn), B, C, mode, p_cutoff, _lib.ptr(w),
+            _lib.ptr(loss), _lib.ptr(dp), C, _lib.ptr(dn), C, _lib.ptr(ws), ws.numel(),
+            _lib.stream_handle(dev)), "ngnn_fix_cr_fwd")
+        ctx.save_for_backward(yp, yn, w)
+        ctx.mode, ctx.p_cutoff, ctx.dp, ctx.dn = mode, p_cutoff, dp, dn
+        ctx.want = (dp is not None, dn is not None)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        yp, yn, w = ctx.saved_tensors
+        B, C = yp.shape
+        dp, dn = ctx.dp, ctx.dn
+        ctx.dp = ctx.dn = None  # handed over once; a second backward recomputes
+        fresh = (ctx.want[0] and dp is None) or (ctx.want[1] and dn is None)
+        if fresh:
+            dp = torch.empty(B, C, dtype=torch.float32, device=yp.device) if ctx.want[0] else None
+            dn = torch.empty(B, C, dtype=torch.float32, device=yp.device) if ctx.want[1] else None
+        if fresh or not getattr(g, "_ngnn_unit", False):
+            g = g.reshape(1).to(torch.float32).contiguous()
+            _lib.check(_lib.load().ngnn_fix_cr_bwd(
+                _lib.ptr(yp), _ld(yp), _lib.ptr(yn), _ld(yn), B, C, ctx.mode, ctx.p_cutoff,
+                _lib.ptr(w), _lib.ptr(g), _lib.ptr(dp), C, _lib.ptr(dn), C,
+                _lib.stream_handle(yp.device)), "ngnn_fix_cr_bwd")
+        return dp, dn, None, None, None
+
+
+def fix_cr(y_pure: torch.Tensor, y_noisy: torch.Tensor, ind_noisy=None, batch_size: int = 512,
+           name: str = "ce", T: float = 1.0, p_cutoff: float = 0.0, use_hard_labels: bool = True,
+           w: torch.Tensor | None = None) -> torch.Tensor:
+    """Drop-in for the reference's ``fix_cr(y_pure, y_noisy, ind_noisy,
+    batch_size, name, T, p_cutoff, use_hard_labels, w)`` (losses.py:206-246):
+    the consistency term between the log-probabilities of the pure and the
+    noisy pass on the rows ``< batch_size`` -- ``name='ce'``: the cross
+    entropy of ``exp(y_noisy)`` (fed as logits, as the reference) against the
+    pseudo label of ``exp(y_pure)`` (its first argmax, or the probabilities
+    themselves with ``use_hard_labels=False``, not detached), masked by
+    ``max >= p_cutoff`` (a factor: the mean runs over all rows), weighted by
+    ``w[:batch_size]``; ``name='l2'``: ``mse_loss(y_noisy, y_pure)``, which
+    reads neither ``w`` nor ``p_cutoff``.  One launch pair
+    (``ngnn_fix_cr_fwd``) writes the loss and both gradients' rows.
+
+    ``B = min(batch_size, rows)``; ``w`` is detached; ``ind_noisy`` and ``T``
+    are accepted and never read (the reference builds a mask from
+    ``ind_noisy`` and drops it), so nothing goes to the host.  fp32, GPU
+    only."""
+    for nm, t in (("y_pure", y_pure), ("y_noisy", y_noisy)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"ngnn.losses.fix_cr: GPU only (no CPU fallback): {nm}")
+    if name not in ("ce", "l2"):
+        raise ValueError(f"fix_cr: name {name!r} is neither 'ce' nor 'l2'")
+    if y_pure.dim() != 2 or y_pure.shape != y_noisy.shape:
+        raise ValueError("y_pure, y_noisy must be [N, C] tensors of the same shape")
+    if y_pure.dtype != torch.float32 or y_noisy.dtype != torch.float32:
+        raise TypeError("fix_cr: only float32 is supported")
+    B = min(int(batch_size), y_pure.size(0))
+    if B <= 0 or y_pure.size(1) == 0:
+        raise ValueError("fix_cr: no rows or no classes")
+    mode = _FIX_CR_MODES[(name, bool(use_hard_labels))]
+    yp, yn = y_pure[:B], y_noisy[:B]
+    if yp.stride(1) != 1:
+        yp = yp.contiguous()
+    if yn.stride(1) != 1:
+        yn = yn.contiguous()
+    wb = None
+    if w is not None and mode != 2:
+        if not w.is_cuda:
+            raise RuntimeError("ngnn.losses.fix_cr: GPU only (no CPU fallback): w")
+        wb = w.detach().reshape(-1)
+        if wb.numel() < B:
+            raise ValueError(f"w holds {wb.numel()} entries, the loss reads {B}")
+        wb = wb[:B].to(torch.float32).contiguous()
+    return _FixCR.apply(yp, yn, wb, mode, float(p_cutoff))
