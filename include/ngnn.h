@@ -1116,6 +1116,58 @@ int ngnn_fix_cr_bwd(const float *lp_pure, int64_t ldp, const float *lp_noisy, in
                     int64_t C, int mode, float p_cutoff, const float *w, const float *grad_scale,
                     float *d_pure, int64_t lddp, float *d_noisy, int64_t lddn, void *stream);
 
+/* ------------------------------------------- flip_label: label-noise injection
+ * Added within ABI 22 (new entries only: nothing existing changed, so the
+ * version did not move).
+ *
+ * ngnn_flip_labels: the per-node draw of flip_label(labels, nbr_classes,
+ * noise_type, prob) of src/utils/noise.py:54-58: out[i] is drawn from row
+ * y[i] of a row-stochastic [C, C] transition matrix M.  The reference draws
+ * np.random.multinomial per node from numpy's global generator; this entry
+ * defines its own draw, a pure function of (seed, i0 + i, y[i], M), bitwise
+ * reproducible and independent of the launch geometry.
+ *   Thresholds (taken by the caller, in float64): cs_k = cumsum(M[l])[k],
+ *   jl = the largest k with M[l][k] > 0;
+ *     T[l][k] = min(floor(cs_k * 2^32), 2^32 - 1)  for k <  jl
+ *     T[l][k] = 2^32 (never reached)               for k >= jl
+ *   passed as thr: uint32 [C, C] row-major (entries k >= jl are not read) and
+ *   last: int32 [C] = jl (clamped to [0, C - 1]).  Rows of thr must be
+ *   non-decreasing over k < jl, as a cumulative sum of non-negatives is.
+ *   Draw, with mix64 the sampler's mixer (splitmix64's finaliser on
+ *   z + 0x9E3779B97F4A7C15), all arithmetic modulo 2^64:
+ *     r = mix64(seed ^ mix64((i0 + i) + 0xA0761D6478BD642F)) >> 32
+ *     out[i] = the number of k with T[y[i]][k] <= r
+ * Class j is drawn with a probability within 2^-32 of M[l][j]; a class of
+ * probability zero is never drawn.  The salt is neither the sampler's
+ * (0x632BE59BD9B4E019) nor the shuffle's second (0xD1B54A32D192ED03).
+ * y: int64 [n]; out: int64 [n], must not alias y (the kernel takes both as
+ * restrict, and an overlapping out is read after it was written); clean: uint8 [n] or NULL,
+ * clean[i] = (out[i] == y[i]), the reference's noise_or_not; counts: int64
+ * [C, C] zeroed by the caller, or NULL (then no histogram work is done):
+ * counts[l][j] += the nodes with y = l and out = j; bad: int32 [1] or NULL: a
+ * label outside [0, C) is copied unchanged (clean 1), added to *bad and left
+ * out of counts (the reference raises IndexError there).  i0: the global
+ * index of y[0] -- a shard [a, b) of the nodes flipped with i0 = a gets
+ * exactly rows [a, b) of the whole vector's flip.
+ * One launch, one lane per node: 1024-thread workgroups, grid =
+ * min(ceil(n / 1024), compute units), a grid-stride loop of four nodes per
+ * thread and trip (a trip of the whole grid covers 4 * 1024 * grid nodes);
+ * thr, last and a [C, C] histogram live in dynamic LDS, 4 C (2 C + 1) bytes,
+ * which limits C to ngnn_flip_labels_max_classes() (128: 128.5 KiB); counts
+ * is gathered per workgroup in LDS and flushed once, non-zero cells only,
+ * with 64-bit vector atomics (integer adds: the result does not depend on
+ * their order).  No workspace, no allocation, no host wait: safe under
+ * stream capture (which bakes seed and i0 in).  n == 0: NGNN_OK, nothing
+ * read, no pointer needed.  Before any launch: a negative n or i0, C < 1, a
+ * NULL y / out / thr / last with n > 0: NGNN_E_ARG; C above the limit:
+ * NGNN_E_SHAPE; n >= 2^31: NGNN_E_RANGE.
+ * Replaces a Python loop of .item(), np.random.multinomial and np.where per
+ * node [ext: numpy]. */
+int ngnn_flip_labels_max_classes(void);
+int ngnn_flip_labels(const int64_t *y, int64_t n, int64_t C, const uint32_t *thr, const int32_t *last,
+                     uint64_t seed, int64_t i0, int64_t *out, uint8_t *clean, int64_t *counts,
+                     int32_t *bad, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,7 +9,9 @@ from . import _lib
 from .block import Block, get_block
 from .models import NGNN, SAGE, SAGEPL, SimpleGCN
 from .nn import GCNConv, Linear, SAGEConv
+from .noise import flip_label, noise_matrix
 from .ops import add_node_noise, segment_aggregate, shuffle_pos, topk_rewire
 
 __all__ = ["Block", "get_block", "NGNN", "SAGE", "SAGEPL", "SimpleGCN", "GCNConv", "Linear", "SAGEConv",
-           "add_node_noise", "segment_aggregate", "shuffle_pos", "topk_rewire", "_lib"]
+           "add_node_noise", "segment_aggregate", "shuffle_pos", "topk_rewire", "flip_label", "noise_matrix",
+           "_lib"]

@@ -150,6 +150,9 @@ SIGNATURES = {
                                _i64, _p, _sz, _p]),
     "ngnn_fix_cr_bwd": (_int, [_p, _i64, _p, _i64, _i64, _i64, _int, ctypes.c_float, _p, _p, _p, _i64, _p,
                                _i64, _p]),
+    # (added within ABI 22: flip_label's per-node draw)
+    "ngnn_flip_labels_max_classes": (_int, []),
+    "ngnn_flip_labels": (_int, [_p, _i64, _i64, _p, _p, ctypes.c_uint64, _i64, _p, _p, _p, _p, _p]),
 }
 
 _lib = None
