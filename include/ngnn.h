@@ -1168,6 +1168,91 @@ int ngnn_flip_labels(const int64_t *y, int64_t n, int64_t C, const uint32_t *thr
                      uint64_t seed, int64_t i0, int64_t *out, uint8_t *clean, int64_t *counts,
                      int32_t *bad, void *stream);
 
+/* ------------------------------------- epoch metrics and per-split accuracy
+ * Added within ABI 22 (new entries only: nothing existing changed, so the
+ * version did not move).
+ *
+ * The tail of every training loop body (pipeline.py:120-125, :164-165:
+ * total_loss += float(loss); total_correct += int(out.argmax(dim=-1).eq(y)
+ * .sum()); total_ratio += 100 * pure_ratio) and of every evaluation
+ * (pipeline.py:182-195: out.argmax(dim=-1, keepdim=True), three index
+ * gathers, three Evaluator.eval) without a host read.
+ *
+ * Argmax rule (both entries), torch.argmax's: the first index of the row's
+ * maximum; +0.0 and -0.0 are equal; a NaN beats every number and the first
+ * NaN wins; a row of -inf gives 0.  bf16 rows are widened exactly.  A row
+ * starts at a multiple of ld elements and needs element alignment only (4 B
+ * for fp32, 2 B for bf16): it is read with single-element loads, a group of
+ * lanes per row (the power of two at or above C / 4, at most 64), which
+ * consecutive lanes coalesce.
+ *
+ * ngnn_step_metrics: one launch, no workspace.  logits: [>= B, C], row
+ * stride ld elements, dtype NGNN_F32 or NGNN_BF16; y: int64 [B]; s0..s3:
+ * float [1] each or NULL (the step's loss, or loss_1, loss_2, pure_ratio_1,
+ * pure_ratio_2); acc: eight 8-byte words owned (and zeroed) by the caller,
+ * 8-byte aligned:
+ *   word 0   int64   += 1 (steps)
+ *   word 1   int64   += rows counted: rows < B whose label is in [0, C)
+ *   word 2   int64   += rows counted whose argmax equals the label
+ *   word 3   int64   += rows whose label is outside [0, C) and is not
+ *                       ignore_index (never counted, never correct)
+ *   word 4+k double  += (double)*s_k for each non-NULL s_k
+ * A row that is not counted is not read.  Words 1..3 receive at most one
+ * 64-bit integer vector atomic per workgroup, after a wave and an LDS
+ * reduction; word 0 and the four sums are written by exactly one thread of
+ * the launch, so a sum is the fp64 sum of the fp32 scalars in launch order
+ * whatever the arrival order of the workgroups.  256-thread workgroups, grid
+ * = min(max(ceil(B * lanes per row / 256), 1), 8 * compute units), a
+ * grid-stride loop.  No allocation and every address an argument: safe under
+ * stream capture.  B == 0 is valid (word 0 and the sums still advance;
+ * logits and y may be NULL then).  Before any launch: B < 0, C < 1, a NULL
+ * acc, a NULL logits or y with B > 0: NGNN_E_ARG; B or C >= 2^31:
+ * NGNN_E_RANGE; ld < C: NGNN_E_SHAPE; an unknown dtype: NGNN_E_DTYPE; acc not
+ * 8-byte aligned: NGNN_E_ALIGN.
+ *
+ * ngnn_split_accuracy: evaluation in one pass over a list of node ids.
+ * logits: [N, C] as above; y: int64 [N]; rows: int64 [M] node ids or NULL (then
+ * M must equal N and entry p is node p; an empty list, M = 0, needs no pointer); bounds: a HOST pointer -- the one
+ * exception to "device pointers only" -- to S + 1 int64, 1 <= S <= 8,
+ * non-decreasing, bounds[0] = 0, bounds[S] = M, read before the call returns
+ * and passed to the kernel by value (so the call stays capturable).  Entries
+ * [bounds[s], bounds[s + 1]) form segment s; ids may repeat and segments may
+ * overlap in ids, and every entry counts (as y_pred[split_idx[k]] does).
+ *   counts: int64 [S][4], overwritten:
+ *     [s][0] evaluated entries: id in [0, N) and label in [0, C)
+ *     [s][1] of those, entries whose argmax equals the label
+ *     [s][2] bad entries: id outside [0, N), or label outside [0, C) and not
+ *            ignore_index
+ *     [s][3] ignored entries (label == ignore_index)
+ *   pred: int64 [M] or NULL: pred[p] = the argmax of row rows[p], -1 for an
+ *     id outside [0, N)
+ *   confusion: int64 [C][C] or NULL, overwritten: confusion[t][q] = evaluated
+ *     entries with label t and argmax q.  Needs C <=
+ *     ngnn_confusion_max_classes() (128): the matrix is gathered per
+ *     workgroup in a uint32 LDS histogram (4 C^2 bytes of dynamic LDS, 64 KiB
+ *     at 128) and its non-zero cells flushed once with 64-bit vector atomics.
+ * The row of an id outside [0, N) is never read (neither its label nor its
+ * logits); the logits row of an ignored or badly labelled entry is read only
+ * when pred is asked for.  Two memset nodes (counts, confusion) and one
+ * launch: 1024-thread workgroups, grid = min(ceil(M * lanes per row / 1024),
+ * 2 * compute units), a grid-stride loop; per-segment counts gathered in LDS
+ * and flushed once per workgroup.  M == 0 or N == 0: NGNN_OK with counts (and
+ * confusion) zeroed and, for N == 0, pred all -1; nothing else is read.
+ * Before anything is enqueued: S outside [1, 8], negative N, M or C < 1, a
+ * NULL bounds or counts, bounds not as stated, rows NULL with M neither N nor 0, a NULL
+ * logits or y with M > 0 and N > 0: NGNN_E_ARG; N, M or C >= 2^31:
+ * NGNN_E_RANGE; ld < C, or confusion with C above the limit: NGNN_E_SHAPE; an
+ * unknown dtype: NGNN_E_DTYPE.
+ * Replaces argmax, index_select, eq, sum and .item() per split, or a copy of
+ * the logits to the host [ext: torch, ogb Evaluator, sklearn accuracy_score]. */
+int ngnn_confusion_max_classes(void);
+int ngnn_step_metrics(const void *logits, int64_t ld, int dtype, int64_t B, int64_t C, const int64_t *y,
+                      int64_t ignore_index, const float *s0, const float *s1, const float *s2, const float *s3,
+                      void *acc, void *stream);
+int ngnn_split_accuracy(const void *logits, int64_t ld, int dtype, int64_t N, int64_t C, const int64_t *y,
+                        int64_t ignore_index, const int64_t *rows, int64_t M, int S, const int64_t *bounds,
+                        int64_t *counts, int64_t *pred, int64_t *confusion, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,8 +5,9 @@ Drop-in for the reference's ``SAGE`` / ``SAGEPL`` / ``SimpleGCN`` (hhilsber/nois
 ``GCNConv`` they call, backed by hand-written HIP kernels for gfx950 behind the
 C ABI in ``include/ngnn.h``.  GPU only: there is no CPU fallback.
 """
-from . import _lib
+from . import _lib, metrics
 from .block import Block, get_block
+from .metrics import EpochMeter, split_accuracy
 from .models import NGNN, SAGE, SAGEPL, SimpleGCN
 from .nn import GCNConv, Linear, SAGEConv
 from .noise import flip_label, noise_matrix
@@ -14,4 +15,4 @@ from .ops import add_node_noise, segment_aggregate, shuffle_pos, topk_rewire
 
 __all__ = ["Block", "get_block", "NGNN", "SAGE", "SAGEPL", "SimpleGCN", "GCNConv", "Linear", "SAGEConv",
            "add_node_noise", "segment_aggregate", "shuffle_pos", "topk_rewire", "flip_label", "noise_matrix",
-           "_lib"]
+           "EpochMeter", "split_accuracy", "metrics", "_lib"]

@@ -153,6 +153,10 @@ SIGNATURES = {
     # (added within ABI 22: flip_label's per-node draw)
     "ngnn_flip_labels_max_classes": (_int, []),
     "ngnn_flip_labels": (_int, [_p, _i64, _i64, _p, _p, ctypes.c_uint64, _i64, _p, _p, _p, _p, _p]),
+    # (added within ABI 22: epoch metrics and per-split accuracy)
+    "ngnn_confusion_max_classes": (_int, []),
+    "ngnn_step_metrics": (_int, [_p, _i64, _int, _i64, _i64, _p, _i64, _p, _p, _p, _p, _p, _p]),
+    "ngnn_split_accuracy": (_int, [_p, _i64, _int, _i64, _i64, _p, _i64, _p, _i64, _int, _p, _p, _p, _p, _p]),
 }
 
 _lib = None

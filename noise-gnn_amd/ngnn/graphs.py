@@ -473,7 +473,11 @@ class GraphedCoTeachingStep(GraphedTrainStep):
     size).  Optimizers: capturable (ngnn.optim.Adam); no Adam fold (two
     models).  ``criterion`` may equally be ``ngnn.losses.CoDiLoss``
     (``algo_type: 'codi'``, pipeline_s.py:51): the same call and 8-tuple,
-    and ``num_remember == 0`` -- one more graph key -- keeps every row."""
+    and ``num_remember == 0`` -- one more graph key -- keeps every row.
+    After a call ``step.out1`` / ``step.out2`` are the two models' detached
+    logits of the graph that just ran (rewritten by its next replay; of a
+    short block, that call's tensors): what ``total_correct_1/2`` need
+    (``ngnn.metrics.EpochMeter``)."""
 
     def __init__(self, model1, optimizer1, model2, optimizer2, criterion, batch_size: int, n_cap: int,
                  e_cap: int, in_dim: int, device, noise_or_not=None, warmup: int = 3):
@@ -487,6 +491,8 @@ class GraphedCoTeachingStep(GraphedTrainStep):
         self.noise_or_not = None if noise_or_not is None else noise_or_not.to(dev, torch.bool)
         self.ind = torch.zeros(self.B, dtype=torch.int64, device=dev)  # n_id[:B] of the loaded block
         self._graphs: dict = {}  # num_remember -> (graph, CTLoss's 8 outputs)
+        self._logits: dict = {}  # num_remember -> that graph's two logits tensors
+        self.out1 = self.out2 = None  # both models' detached logits of the step that just ran
 
     def num_remember(self, forget_rate: float, B: int | None = None) -> int:
         return int((1 - forget_rate) * (self.B if B is None else B))
@@ -494,6 +500,7 @@ class GraphedCoTeachingStep(GraphedTrainStep):
     def _ct_fwd_bwd(self, forget_rate):
         out1 = self.model(self.x, self.ei)
         out2 = self.model2(self.x, self.ei)
+        self.out1, self.out2 = out1.detach(), out2.detach()
         res = self.criterion(out1, out2, self.y, forget_rate, self.ind, self.noise_or_not, batch_size=self.B)
         if self._one is None:
             from .losses import unit_grad
@@ -562,6 +569,7 @@ class GraphedCoTeachingStep(GraphedTrainStep):
         finally:
             _optim._slot_gate = None
         self._graphs[self.num_remember(forget_rate)] = (g, outs)
+        self._logits[self.num_remember(forget_rate)] = (self.out1, self.out2)
         block_cache.clear()
         torch.cuda.synchronize()
         if snap is not None:
@@ -594,12 +602,14 @@ class GraphedCoTeachingStep(GraphedTrainStep):
         g, outs = self._graphs[nr]
         self._load_ct(x, edge_index, y, n_id, zero_copy=self.zero_copy)
         g.replay()
+        self.out1, self.out2 = self._logits[nr]
         return outs
 
     def _eager(self, x, edge_index, y, n_id, forget_rate, bs):
         x = x.materialize() if isinstance(x, IndexedRows) else x
         out1 = self.model(x, edge_index)
         out2 = self.model2(x, edge_index)
+        self.out1, self.out2 = out1.detach(), out2.detach()
         res = self.criterion(out1, out2, y, forget_rate, n_id, self.noise_or_not, batch_size=bs)
         for o in (self.opt, self.opt2):
             o.zero_grad(set_to_none=False)
