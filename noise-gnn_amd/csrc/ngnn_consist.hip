@@ -11,21 +11,10 @@
 // ngnn_fix_cr_fwd / _bwd: one wave per row r < B; the row terms go to the
 //   workspace and one workgroup adds them in a fixed order (second launch),
 //   as ngnn_bc_loss_fwd.  The backward recomputes from the inputs.
-#include "ngnn_internal.h"
+#include "ngnn_rows.h"
 
 namespace ngnn {
 namespace {
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ float wave_maxf(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
 
 // (the reference adds the Python double 1e-5 to a float tensor: rounded once)
 constexpr float kEntEps = static_cast<float>(1e-5);
@@ -34,8 +23,7 @@ __global__ __launch_bounds__(256) void k_nbr_unc(const float *__restrict__ logp,
                                                  int C, const int32_t *__restrict__ rowptr,
                                                  const int32_t *__restrict__ col, int R, float lg,
                                                  float epsilon, float *__restrict__ w) {
-    const int lane = threadIdx.x & 63;
-    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = wave_lane(), i = wave_row();
     if (i >= R) return;
     const int beg = rowptr[i], end = rowptr[i + 1];
     const float den = static_cast<float>(end - beg) + epsilon;
@@ -99,8 +87,7 @@ __global__ __launch_bounds__(256) void k_fixcr_rows(const float *__restrict__ yp
                                                     float *__restrict__ part, const float *__restrict__ g,
                                                     float *__restrict__ dp, int64_t lddp,
                                                     float *__restrict__ dn, int64_t lddn) {
-    const int lane = threadIdx.x & 63;
-    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = wave_lane(), r = wave_row();
     if (r >= B) return;
     const float *ypr = yp + static_cast<int64_t>(r) * ldp;
     const float *ynr = yn + static_cast<int64_t>(r) * ldn;
@@ -181,16 +168,10 @@ __global__ __launch_bounds__(256) void k_fixcr_rows(const float *__restrict__ yp
 // one workgroup adds the row terms in a fixed order -> deterministic
 __global__ __launch_bounds__(256) void k_fixcr_sum(const float *__restrict__ part, int B, float denom,
                                                    float *__restrict__ loss) {
-    float s = 0.0f;
-    for (int i = threadIdx.x; i < B; i += 256) s += part[i];
-    __shared__ float ss[256];
-    ss[threadIdx.x] = s;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if (threadIdx.x < h) ss[threadIdx.x] += ss[threadIdx.x + h];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *loss = ss[0] / denom;
+    __shared__ float tree[1][256];
+    float s[1];
+    block_sum(tree, s, B, [&](int i, float(&a)[1]) { a[0] += part[i]; });
+    if (threadIdx.x == 0) *loss = s[0] / denom;
 }
 
 constexpr int64_t kMaxC = 65535;
@@ -219,9 +200,7 @@ extern "C" int ngnn_nbr_uncertainty(const float *logp, int64_t ld, int64_t n_row
     // (col is read only where a list is not empty: a CSR without edges may pass NULL)
     NGNN_RETURN_IF(!logp || !rowptr || !w, NGNN_E_ARG);
     const float lg = log2f(static_cast<float>(nbr_classes));
-    hipLaunchKernelGGL(k_nbr_unc, dim3(static_cast<unsigned>(ceil_div(R, 4))), dim3(256), 0,
-                       as_stream(stream), logp, ld, (int)n_rows, (int)C, rowptr, col, (int)R, lg, epsilon,
-                       w);
+    launch_rows(k_nbr_unc, R, as_stream(stream), logp, ld, (int)n_rows, (int)C, rowptr, col, (int)R, lg, epsilon, w);
     return launch_status();
 }
 
@@ -239,9 +218,8 @@ extern "C" int ngnn_fix_cr_fwd(const float *lp_pure, int64_t ldp, const float *l
     NGNN_RETURN_IF(ws_bytes < ngnn_fix_cr_workspace_bytes(B) || !aligned(ws, 16), NGNN_E_WORKSPACE);
     float *part = static_cast<float *>(ws);
     hipStream_t st = as_stream(stream);
-    hipLaunchKernelGGL(k_fixcr_rows, dim3(static_cast<unsigned>(ceil_div(B, 4))), dim3(256), 0, st, lp_pure,
-                       ldp, lp_noisy, ldn, (int)B, (int)C, mode, p_cutoff, w, part,
-                       static_cast<const float *>(nullptr), d_pure, lddp, d_noisy, lddn);
+    launch_rows(k_fixcr_rows, B, st, lp_pure, ldp, lp_noisy, ldn, (int)B, (int)C, mode, p_cutoff, w, part, nullptr,
+                d_pure, lddp, d_noisy, lddn);
     rc = launch_status();
     if (rc) return rc;
     const float denom = mode == kL2 ? static_cast<float>(B) * static_cast<float>(C) : static_cast<float>(B);
@@ -257,8 +235,7 @@ extern "C" int ngnn_fix_cr_bwd(const float *lp_pure, int64_t ldp, const float *l
     int rc = fixcr_check(lp_pure, ldp, lp_noisy, ldn, B, C, mode, d_pure, lddp, d_noisy, lddn);
     if (rc) return rc;
     if (!d_pure && !d_noisy) return NGNN_OK;  // no gradient wanted: nothing to launch
-    hipLaunchKernelGGL(k_fixcr_rows, dim3(static_cast<unsigned>(ceil_div(B, 4))), dim3(256), 0,
-                       as_stream(stream), lp_pure, ldp, lp_noisy, ldn, (int)B, (int)C, mode, p_cutoff, w,
-                       static_cast<float *>(nullptr), grad_scale, d_pure, lddp, d_noisy, lddn);
+    launch_rows(k_fixcr_rows, B, as_stream(stream), lp_pure, ldp, lp_noisy, ldn, (int)B, (int)C, mode, p_cutoff, w,
+                nullptr, grad_scale, d_pure, lddp, d_noisy, lddn);
     return launch_status();
 }

@@ -22,6 +22,7 @@
 // launch (deterministic); the backward scatters with float atomics into
 // caller-prepared buffers (duplicates accumulate; distinct indices: one add
 // per element onto the caller's value, bitwise reproducible).
+#include "ngnn_rows.h"
 #include "ngnn_sample_dev.h"
 
 namespace ngnn {
@@ -34,12 +35,6 @@ constexpr int kNarrowF = 256;
 // (key a, column / position ia) before (key b, ib)
 __device__ __forceinline__ int before(uint64_t a, int ia, uint64_t b, int ib) {
     return (a < b || (a == b && ia < ib)) ? 1 : 0;
-}
-
-__device__ __forceinline__ int wave_sum_int(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
 }
 
 // One wave per row, 4 rows per workgroup, F <= 64 NK.  Lane l holds columns
@@ -158,7 +153,7 @@ __global__ __launch_bounds__(256) void k_shuffle_narrow(const float *__restrict_
     int total = 0;
 #pragma unroll
     for (int k = 0; k < NK; ++k) total += sel[k] ? rho[k] : 0;
-    if (wave_sum_int(total) != m * (m - 1) / 2) {  // (wave-uniform) the exact ranks
+    if (wave_sum(total) != m * (m - 1) / 2) {  // (wave-uniform) the exact ranks
         uint64_t k2[NK];
 #pragma unroll
         for (int k = 0; k < NK; ++k) {
@@ -235,12 +230,6 @@ __global__ __launch_bounds__(256) void k_shuffle_wide(const float *__restrict__ 
 // ---------------------------------------------------------------------------
 // contrastive discriminator loss
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // max(x, 0) + log1p(exp(-|x|)); NaN stays NaN
 __device__ __forceinline__ double softplus(double x) {
     return (x > 0.0 ? x : 0.0) + log1p(exp(-fabs(x)));
@@ -260,8 +249,7 @@ __global__ __launch_bounds__(256) void k_contrast_rows(const float *__restrict__
                                                        int64_t n_rows, int F,
                                                        const int64_t *__restrict__ idx, int M,
                                                        double *__restrict__ ws, int32_t *__restrict__ bad) {
-    const int lane = threadIdx.x & 63;
-    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = wave_lane(), i = wave_row();
     if (i >= M) return;
     const int64_t r = idx[i];
     double a = NAN, b = NAN;
@@ -288,24 +276,14 @@ __global__ __launch_bounds__(256) void k_contrast_rows(const float *__restrict__
 // one workgroup adds the row terms in a fixed order -> deterministic
 __global__ __launch_bounds__(256) void k_contrast_sum(const double *__restrict__ ws, int M,
                                                       float *__restrict__ out) {
-    double sp = 0.0, sn = 0.0;
-    for (int i = threadIdx.x; i < M; i += 256) {
-        sp += softplus(-ws[i]);
-        sn += softplus(ws[M + i]);
-    }
-    __shared__ double tp[256], tn[256];
-    tp[threadIdx.x] = sp;
-    tn[threadIdx.x] = sn;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) {
-            tp[threadIdx.x] += tp[threadIdx.x + s];
-            tn[threadIdx.x] += tn[threadIdx.x + s];
-        }
-        __syncthreads();
-    }
+    __shared__ double tree[2][256];
+    double t[2];  // positive terms, negative terms
+    block_sum(tree, t, M, [&](int i, double(&a)[2]) {
+        a[0] += softplus(-ws[i]);
+        a[1] += softplus(ws[M + i]);
+    });
     if (threadIdx.x == 0) {
-        const double p = tp[0] / M, n = tn[0] / M;
+        const double p = t[0] / M, n = t[1] / M;
         out[0] = static_cast<float>(p + n);
         out[1] = static_cast<float>(p);
         out[2] = static_cast<float>(n);
@@ -323,8 +301,7 @@ __global__ __launch_bounds__(256) void k_contrast_bwd(const float *__restrict__ 
                                                       const float *__restrict__ g, float *__restrict__ dh,
                                                       int64_t lddh, float *__restrict__ dhp, int64_t lddp,
                                                       float *__restrict__ dhn, int64_t lddn) {
-    const int lane = threadIdx.x & 63;
-    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = wave_lane(), i = wave_row();
     if (i >= M) return;
     const int64_t r = idx[i];
     if (r < 0 || r >= n_rows) return;
@@ -386,8 +363,7 @@ extern "C" int ngnn_contrast_fwd(const float *h, int64_t ldh, const float *hp, i
     NGNN_RETURN_IF(ws_bytes < ngnn_contrast_workspace_bytes(M) || !aligned(ws, 16), NGNN_E_WORKSPACE);
     double *w = static_cast<double *>(ws);
     hipStream_t st = as_stream(stream);
-    hipLaunchKernelGGL(k_contrast_rows, dim3(static_cast<unsigned>(ceil_div(M, 4))), dim3(256), 0, st, h,
-                       ldh, hp, ldp, hn, ldn, n_rows, (int)F, idx, (int)M, w, bad);
+    launch_rows(k_contrast_rows, M, st, h, ldh, hp, ldp, hn, ldn, n_rows, (int)F, idx, (int)M, w, bad);
     int rc = launch_status();
     if (rc) return rc;
     hipLaunchKernelGGL(k_contrast_sum, dim3(1), dim3(256), 0, st, w, (int)M, out);
@@ -405,8 +381,7 @@ extern "C" int ngnn_contrast_bwd(const float *h, int64_t ldh, const float *hp, i
     NGNN_RETURN_IF((dh && lddh < F) || (dhp && lddp < F) || (dhn && lddn < F), NGNN_E_SHAPE);
     NGNN_RETURN_IF(!fits_i32(n_rows) || !fits_i32(F) || !fits_i32(M), NGNN_E_RANGE);
     if (!dh && !dhp && !dhn) return NGNN_OK;
-    hipLaunchKernelGGL(k_contrast_bwd, dim3(static_cast<unsigned>(ceil_div(M, 4))), dim3(256), 0,
-                       as_stream(stream), h, ldh, hp, ldp, hn, ldn, n_rows, (int)F, idx, (int)M,
-                       static_cast<const double *>(ws), grad_scale, dh, lddh, dhp, lddp, dhn, lddn);
+    launch_rows(k_contrast_bwd, M, as_stream(stream), h, ldh, hp, ldp, hn, ldn, n_rows, (int)F, idx, (int)M,
+                static_cast<const double *>(ws), grad_scale, dh, lddh, dhp, lddp, dhn, lddn);
     return launch_status();
 }

@@ -10,7 +10,7 @@
 // backward: d x_r[c] = g (softmax(x_r)[c] - [c == y_r]) / #valid for r < B,
 //           0 for ignored rows; rows >= B are not written (the caller keeps
 //           them zero).  One wave per row.
-#include "ngnn_internal.h"
+#include "ngnn_rows.h"
 
 namespace ngnn {
 namespace {
@@ -19,42 +19,18 @@ namespace {
 // (B^2 / 4 reads): above this many seed rows the O(B) three-launch path
 constexpr int64_t kXentFusedMaxB = 4096;
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ float wave_maxf(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-
-// log-sum-exp of one row (torch's log_softmax order: max, then sum of
-// exp(x - max)); a NaN anywhere makes the sum NaN
-__device__ __forceinline__ float row_lse(const float *__restrict__ xr, int C, int lane) {
-    float m = -INFINITY;
-    for (int c = lane; c < C; c += 64) m = fmaxf(m, xr[c]);
-    m = wave_maxf(m);
-    float s = 0.0f;
-    for (int c = lane; c < C; c += 64) s += expf(xr[c] - m);
-    s = wave_sum(s);
-    return m + logf(s);
-}
-
 // one wave per row: ws[r] = row loss (0 if ignored), ws[B + r] = 1/0 valid
 __global__ __launch_bounds__(256) void k_xent_rows(const float *__restrict__ x, int64_t ld, int B,
                                                    int C, const int64_t *__restrict__ y,
                                                    int64_t ignore, float *__restrict__ ws) {
-    const int lane = threadIdx.x & 63;
-    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = wave_lane(), r = wave_row();
     if (r >= B) return;
     const int64_t t = y[r];
     float l = 0.0f, v = 0.0f;
     if (t != ignore) {
         const float *xr = x + static_cast<int64_t>(r) * ld;
         const float lse = row_lse(xr, C, lane);
-        l = (t >= 0 && t < C) ? lse - xr[t] : NAN;  // out-of-range label: NaN, no OOB read
+        l = row_nll(xr, lse, t, C);
         v = 1.0f;
     }
     if (lane == 0) {
@@ -69,25 +45,15 @@ __global__ __launch_bounds__(256) void k_xent_rows(const float *__restrict__ x, 
 __global__ __launch_bounds__(256) void k_xent_sum(const float *__restrict__ ws, int B,
                                                   float *__restrict__ loss,
                                                   float *__restrict__ count) {
-    float s = 0.0f, n = 0.0f;
-    for (int i = threadIdx.x; i < B; i += 256) {
-        s += ws[i];
-        n += ws[B + i];
-    }
-    __shared__ float ss[256], sn[256];
-    ss[threadIdx.x] = s;
-    sn[threadIdx.x] = n;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if (threadIdx.x < h) {
-            ss[threadIdx.x] += ss[threadIdx.x + h];
-            sn[threadIdx.x] += sn[threadIdx.x + h];
-        }
-        __syncthreads();
-    }
+    __shared__ float tree[2][256];
+    float t[2];  // loss sum, valid rows
+    block_sum(tree, t, B, [&](int i, float(&a)[2]) {
+        a[0] += ws[i];
+        a[1] += ws[B + i];
+    });
     if (threadIdx.x == 0) {
-        *loss = ss[0] / sn[0];  // 0/0 = NaN when every row is ignored, as torch
-        *count = sn[0];
+        *loss = t[0] / t[1];  // 0/0 = NaN when every row is ignored, as torch
+        *count = t[1];
     }
 }
 
@@ -97,8 +63,7 @@ __global__ __launch_bounds__(256) void k_xent_bwd(const float *__restrict__ x, i
                                                   const float *__restrict__ g,
                                                   const float *__restrict__ count,
                                                   float *__restrict__ dx, int64_t ldd) {
-    const int lane = threadIdx.x & 63;
-    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = wave_lane(), r = wave_row();
     if (r >= B) return;
     const float *xr = x + static_cast<int64_t>(r) * ld;
     float *dr = dx + static_cast<int64_t>(r) * ldd;
@@ -144,20 +109,14 @@ __global__ __launch_bounds__(256) void k_xent_fused(const float *__restrict__ x,
                                                     float *__restrict__ loss,
                                                     float *__restrict__ count,
                                                     float *__restrict__ dx, int64_t ldd) {
-    __shared__ float s_red[256];
+    __shared__ float s_red[1][256];
     __shared__ float s_row[4];
     __shared__ int s_last;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    float nv = 0.0f;
-    for (int i = threadIdx.x; i < B; i += 256) nv += (y[i] != ignore) ? 1.0f : 0.0f;
-    s_red[threadIdx.x] = nv;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if (threadIdx.x < h) s_red[threadIdx.x] += s_red[threadIdx.x + h];
-        __syncthreads();
-    }
-    const float cnt = s_red[0];
-    const int r = blockIdx.x * 4 + wv;
+    const int lane = wave_lane(), wv = threadIdx.x >> 6;
+    float red[1];
+    block_sum(s_red, red, B, [&](int i, float(&a)[1]) { a[0] += (y[i] != ignore) ? 1.0f : 0.0f; });
+    const float cnt = red[0];
+    const int r = wave_row();
     float l = 0.0f;
     if (r < B) {
         const float *xr = x + static_cast<int64_t>(r) * ld;
@@ -167,7 +126,7 @@ __global__ __launch_bounds__(256) void k_xent_fused(const float *__restrict__ x,
             for (int c = lane; c < C; c += 64) dr[c] = 0.0f;
         } else {
             const float lse = row_lse(xr, C, lane);
-            l = (t >= 0 && t < C) ? lse - xr[t] : NAN;  // out-of-range label: NaN, no OOB read
+            l = row_nll(xr, lse, t, C);
             for (int c = lane; c < C; c += 64)
                 dr[c] = (expf(xr[c] - lse) - (c == t ? 1.0f : 0.0f)) / cnt;
         }
@@ -187,17 +146,12 @@ __global__ __launch_bounds__(256) void k_xent_fused(const float *__restrict__ x,
     }
     __syncthreads();
     if (!s_last) return;
-    float s = 0.0f;
-    for (int i = threadIdx.x; i < static_cast<int>(gridDim.x); i += 256)
-        s += __hip_atomic_load(part + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s_red[threadIdx.x] = s;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if (threadIdx.x < h) s_red[threadIdx.x] += s_red[threadIdx.x + h];
-        __syncthreads();
-    }
+    // (s_red again: the two barriers above separate it from cnt's read)
+    block_sum(s_red, red, static_cast<int>(gridDim.x), [&](int i, float(&a)[1]) {
+        a[0] += __hip_atomic_load(part + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    });
     if (threadIdx.x == 0) {
-        *loss = s_red[0] / cnt;  // 0/0 = NaN when every row is ignored, as torch
+        *loss = red[0] / cnt;  // 0/0 = NaN when every row is ignored, as torch
         *count = cnt;
         *ticket = 0u;
     }
@@ -220,8 +174,7 @@ __global__ __launch_bounds__(256) void k_ct_rows(const float *__restrict__ y1, i
                                                  const float *__restrict__ y2, int64_t ld2, int B,
                                                  int C, const int64_t *__restrict__ t,
                                                  int64_t ignore, float *__restrict__ ws) {
-    const int lane = threadIdx.x & 63;
-    const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = wave_lane(), g = wave_row();
     if (g >= 2 * B) return;
     const int m = g >= B, r = g - m * B;
     const float *xr = (m ? y2 : y1) + static_cast<int64_t>(r) * (m ? ld2 : ld1);
@@ -229,7 +182,7 @@ __global__ __launch_bounds__(256) void k_ct_rows(const float *__restrict__ y1, i
     float l = 0.0f, v = 0.0f;
     if (c != ignore) {
         const float lse = row_lse(xr, C, lane);
-        l = (c >= 0 && c < C) ? lse - xr[c] : NAN;
+        l = row_nll(xr, lse, c, C);
         v = 1.0f;
     }
     if (lane == 0) {
@@ -238,8 +191,10 @@ __global__ __launch_bounds__(256) void k_ct_rows(const float *__restrict__ y1, i
     }
 }
 
-__device__ __forceinline__ uint32_t order_key(float f) {
-    if (f != f) return 0xffffffffu;  // NaN last
+// ascending losses by their bits (-0 before +0), NaN last.  (ngnn_metrics'
+// argmax_order_key makes -0 == +0, as torch.argmax compares: not this one)
+__device__ __forceinline__ uint32_t loss_order_key(float f) {
+    if (f != f) return 0xffffffffu;
     const uint32_t u = __float_as_uint(f);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
@@ -257,13 +212,13 @@ __global__ __launch_bounds__(1024) void k_ct_select(float *__restrict__ ws,
                                                     float *__restrict__ out,
                                                     int *__restrict__ err) {
     __shared__ uint64_t key[kCtMaxB];
-    __shared__ float rs[1024], rc[1024], rp[1024];
+    __shared__ float tree[3][1024];
     const int m = blockIdx.x, o = 1 - m, tid = threadIdx.x;
     int P = 1;
     while (P < B) P <<= 1;
     const float *l = skey + m * B;
     for (int i = tid; i < P; i += 1024)
-        key[i] = i < B ? (static_cast<uint64_t>(order_key(l[i])) << 32) | static_cast<uint32_t>(i)
+        key[i] = i < B ? (static_cast<uint64_t>(loss_order_key(l[i])) << 32) | static_cast<uint32_t>(i)
                        : ~0ull;
     __syncthreads();
     for (int k = 2; k <= P; k <<= 1) {
@@ -288,36 +243,24 @@ __global__ __launch_bounds__(1024) void k_ct_select(float *__restrict__ ws,
     for (int i = tid; i < B; i += 1024) sel[i] = 0.0f;
     __syncthreads();
     const float *lo = ws + o * B, *vo = ws + 2 * B + o * B;
-    float s = 0.0f, c = 0.0f, p = 0.0f;
+    float t[3];  // model o's loss sum and valid rows over the kept rows, model m's clean rows
     int bad = 0;
-    for (int j = tid; j < R; j += 1024) {
+    block_sum(tree, t, R, [&](int j, float(&a)[3]) {
         const int r = static_cast<int>(key[j] & 0xffffffffu);
         sel[r] = 1.0f;
-        s += lo[r];  // ignored rows hold 0
-        c += vo[r];
+        a[0] += lo[r];  // ignored rows hold 0
+        a[1] += vo[r];
         if (clean) {
             const int64_t g = ind ? ind[r] : r;
             if (g < 0 || g >= n_clean) bad = 1;
-            else p += clean[g] ? 1.0f : 0.0f;
+            else a[2] += clean[g] ? 1.0f : 0.0f;
         }
-    }
-    rs[tid] = s;
-    rc[tid] = c;
-    rp[tid] = p;
+    });
     if (bad) atomicOr(err, 1);
-    __syncthreads();
-    for (int h = 512; h > 0; h >>= 1) {
-        if (tid < h) {
-            rs[tid] += rs[tid + h];
-            rc[tid] += rc[tid + h];
-            rp[tid] += rp[tid + h];
-        }
-        __syncthreads();
-    }
     if (tid == 0) {
-        out[o] = rs[0] / rc[0];                     // 0/0 = NaN, as torch's empty mean
-        out[2 + m] = clean ? rp[0] / static_cast<float>(R) : NAN;
-        ws[6 * B + o] = rc[0];
+        out[o] = t[0] / t[1];                       // 0/0 = NaN, as torch's empty mean
+        out[2 + m] = clean ? t[2] / static_cast<float>(R) : NAN;
+        ws[6 * B + o] = t[1];
     }
 }
 
@@ -328,8 +271,7 @@ __global__ __launch_bounds__(256) void k_ct_bwd(const float *__restrict__ y, int
                                                 const float *__restrict__ ws, int m,
                                                 const float *__restrict__ g, float *__restrict__ dy,
                                                 int64_t ldd) {
-    const int lane = threadIdx.x & 63;
-    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = wave_lane(), r = wave_row();
     if (r >= B) return;
     const float *xr = y + static_cast<int64_t>(r) * ld;
     float *dr = dy + static_cast<int64_t>(r) * ldd;
@@ -361,8 +303,7 @@ __global__ __launch_bounds__(256) void k_codi_rows(const float *__restrict__ y1,
                                                    int64_t ignore, float co_lambda,
                                                    float *__restrict__ ws, float *__restrict__ skey,
                                                    float *__restrict__ js_out) {
-    const int lane = threadIdx.x & 63;
-    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = wave_lane(), r = wave_row();
     if (r >= B) return;
     const float *a = y1 + static_cast<int64_t>(r) * ld1;
     const float *b = y2 + static_cast<int64_t>(r) * ld2;
@@ -378,9 +319,8 @@ __global__ __launch_bounds__(256) void k_codi_rows(const float *__restrict__ y1,
     const int64_t c = t[r];
     float l1 = 0.0f, l2 = 0.0f, v = 0.0f;
     if (c != ignore) {
-        const bool ok = c >= 0 && c < C;  // out-of-range label: NaN, no OOB read
-        l1 = ok ? lse1 - a[c] : NAN;
-        l2 = ok ? lse2 - b[c] : NAN;
+        l1 = row_nll(a, lse1, c, C);
+        l2 = row_nll(b, lse2, c, C);
         v = 1.0f;
     }
     if (lane == 0) {
@@ -411,8 +351,7 @@ __global__ __launch_bounds__(256) void k_bc_rows(const float *__restrict__ x, in
                                                  const float *__restrict__ cinv, int64_t ldc,
                                                  float *__restrict__ part, const float *__restrict__ g,
                                                  float *__restrict__ dx, int64_t ldd) {
-    const int lane = threadIdx.x & 63;
-    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = wave_lane(), r = wave_row();
     if (r >= B) return;
     const float *xr = x + static_cast<int64_t>(r) * ld;
     const int64_t t = y[r];
@@ -442,16 +381,10 @@ __global__ __launch_bounds__(256) void k_bc_rows(const float *__restrict__ x, in
 // one workgroup adds the row partials in a fixed order -> deterministic
 __global__ __launch_bounds__(256) void k_bc_sum(const float *__restrict__ part, int B, int C,
                                                 float *__restrict__ loss) {
-    float s = 0.0f;
-    for (int i = threadIdx.x; i < B; i += 256) s += part[i];
-    __shared__ float ss[256];
-    ss[threadIdx.x] = s;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if (threadIdx.x < h) ss[threadIdx.x] += ss[threadIdx.x + h];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *loss = -ss[0] / (static_cast<float>(B) * static_cast<float>(C));
+    __shared__ float tree[1][256];
+    float s[1];
+    block_sum(tree, s, B, [&](int i, float(&a)[1]) { a[0] += part[i]; });
+    if (threadIdx.x == 0) *loss = -s[0] / (static_cast<float>(B) * static_cast<float>(C));
 }
 
 }  // namespace
@@ -471,8 +404,7 @@ extern "C" int ngnn_seed_xent_fwd(const float *logits, int64_t ld, int64_t B, in
     NGNN_RETURN_IF(!fits_i32(B) || !fits_i32(C), NGNN_E_RANGE);
     NGNN_RETURN_IF(ws_bytes < ngnn_seed_xent_workspace_bytes(B) || !aligned(ws, 16), NGNN_E_WORKSPACE);
     float *w = static_cast<float *>(ws);
-    hipLaunchKernelGGL(k_xent_rows, dim3(static_cast<unsigned>(ceil_div(B, 4))), dim3(256), 0,
-                       as_stream(stream), logits, ld, (int)B, (int)C, y, ignore_index, w);
+    launch_rows(k_xent_rows, B, as_stream(stream), logits, ld, (int)B, (int)C, y, ignore_index, w);
     int rc = launch_status();
     if (rc) return rc;
     hipLaunchKernelGGL(k_xent_sum, dim3(1), dim3(256), 0, as_stream(stream), w, (int)B, loss, count);
@@ -493,19 +425,15 @@ extern "C" int ngnn_seed_xent_fwd_grad(const float *logits, int64_t ld, int64_t 
     if (B > kXentFusedMaxB) {
         // large seed sets (a full-batch loader): rows, fixed-order sum, then the
         // gradient rows at unit scale -- O(B) label reads
-        const unsigned grid = static_cast<unsigned>(ceil_div(B, 4));
-        hipLaunchKernelGGL(k_xent_rows, dim3(grid), dim3(256), 0, st, logits, ld, (int)B, (int)C, y,
-                           ignore_index, w);
+        launch_rows(k_xent_rows, B, st, logits, ld, (int)B, (int)C, y, ignore_index, w);
         hipLaunchKernelGGL(k_xent_sum, dim3(1), dim3(256), 0, st, w, (int)B, loss, count);
-        hipLaunchKernelGGL(k_xent_bwd, dim3(grid), dim3(256), 0, st, logits, ld, (int)B, (int)C, y,
-                           ignore_index, w, nullptr, count, dlogits, ldd);
+        launch_rows(k_xent_bwd, B, st, logits, ld, (int)B, (int)C, y, ignore_index, w, nullptr, count, dlogits, ldd);
         return launch_status();
     }
     // the ticket sits past the row-loss area of ngnn_seed_xent_fwd (3 B floats)
     uint32_t *ticket = reinterpret_cast<uint32_t *>(w + 3 * B);
-    hipLaunchKernelGGL(k_xent_fused, dim3(static_cast<unsigned>(ceil_div(B, 4))), dim3(256), 0,
-                       as_stream(stream), logits, ld, (int)B, (int)C, y, ignore_index, w, ticket,
-                       loss, count, dlogits, ldd);
+    launch_rows(k_xent_fused, B, st, logits, ld, (int)B, (int)C, y, ignore_index, w, ticket, loss, count,
+                dlogits, ldd);
     return launch_status();
 }
 
@@ -517,9 +445,8 @@ extern "C" int ngnn_seed_xent_bwd(const float *logits, int64_t ld, int64_t B, in
                    NGNN_E_ARG);
     NGNN_RETURN_IF(ld < C || ldd < C, NGNN_E_SHAPE);
     NGNN_RETURN_IF(!fits_i32(B) || !fits_i32(C), NGNN_E_RANGE);
-    hipLaunchKernelGGL(k_xent_bwd, dim3(static_cast<unsigned>(ceil_div(B, 4))), dim3(256), 0,
-                       as_stream(stream), logits, ld, (int)B, (int)C, y, ignore_index,
-                       static_cast<const float *>(ws), grad_scale, count, dlogits, ldd);
+    launch_rows(k_xent_bwd, B, as_stream(stream), logits, ld, (int)B, (int)C, y, ignore_index,
+                static_cast<const float *>(ws), grad_scale, count, dlogits, ldd);
     return launch_status();
 }
 
@@ -542,8 +469,7 @@ extern "C" int ngnn_ct_loss_fwd(const float *y1, int64_t ld1, const float *y2, i
     NGNN_RETURN_IF(ws_bytes < ngnn_ct_loss_workspace_bytes(B) || !aligned(ws, 16), NGNN_E_WORKSPACE);
     float *w = static_cast<float *>(ws);
     hipStream_t st = as_stream(stream);
-    hipLaunchKernelGGL(k_ct_rows, dim3(static_cast<unsigned>(ceil_div(2 * B, 4))), dim3(256), 0, st,
-                       y1, ld1, y2, ld2, (int)B, (int)C, y_noise, ignore_index, w);
+    launch_rows(k_ct_rows, 2 * B, st, y1, ld1, y2, ld2, (int)B, (int)C, y_noise, ignore_index, w);
     int rc = launch_status();
     if (rc) return rc;
     hipLaunchKernelGGL(k_ct_select, dim3(2), dim3(1024), 0, st, w, w, (int)B, (int)num_remember, ind,
@@ -558,9 +484,8 @@ extern "C" int ngnn_ct_loss_bwd(int model, const float *y, int64_t ld, int64_t B
     NGNN_RETURN_IF(B <= 0 || C <= 0, NGNN_E_ARG);
     NGNN_RETURN_IF(ld < C || ldd < C || B > kCtMaxB, NGNN_E_SHAPE);
     NGNN_RETURN_IF(!fits_i32(C), NGNN_E_RANGE);
-    hipLaunchKernelGGL(k_ct_bwd, dim3(static_cast<unsigned>(ceil_div(B, 4))), dim3(256), 0,
-                       as_stream(stream), y, ld, (int)B, (int)C, y_noise, ignore_index,
-                       static_cast<const float *>(ws), model, grad, dy, ldd);
+    launch_rows(k_ct_bwd, B, as_stream(stream), y, ld, (int)B, (int)C, y_noise, ignore_index,
+                static_cast<const float *>(ws), model, grad, dy, ldd);
     return launch_status();
 }
 
@@ -586,8 +511,8 @@ extern "C" int ngnn_codi_loss_fwd(const float *y1, int64_t ld1, const float *y2,
     // an empty selection keeps every row (losses.py:125-128)
     const int R = static_cast<int>(num_remember == 0 ? B : num_remember);
     hipStream_t st = as_stream(stream);
-    hipLaunchKernelGGL(k_codi_rows, dim3(static_cast<unsigned>(ceil_div(B, 4))), dim3(256), 0, st, y1,
-                       ld1, y2, ld2, (int)B, (int)C, y_noise, ignore_index, co_lambda, w, skey, js_out);
+    launch_rows(k_codi_rows, B, st, y1, ld1, y2, ld2, (int)B, (int)C, y_noise, ignore_index, co_lambda, w, skey,
+                js_out);
     int rc = launch_status();
     if (rc) return rc;
     hipLaunchKernelGGL(k_ct_select, dim3(2), dim3(1024), 0, st, w, skey, (int)B, R, ind, noise_or_not,
@@ -615,9 +540,7 @@ extern "C" int ngnn_bc_loss_fwd(const float *logits, int64_t ld, int64_t B, int6
     NGNN_RETURN_IF(ws_bytes < ngnn_bc_loss_workspace_bytes(B) || !aligned(ws, 16), NGNN_E_WORKSPACE);
     float *w = static_cast<float *>(ws);
     hipStream_t st = as_stream(stream);
-    hipLaunchKernelGGL(k_bc_rows, dim3(static_cast<unsigned>(ceil_div(B, 4))), dim3(256), 0, st, logits,
-                       ld, (int)B, (int)C, labels, Cinv, ldc, w, static_cast<const float *>(nullptr),
-                       dlogits, ldd);
+    launch_rows(k_bc_rows, B, st, logits, ld, (int)B, (int)C, labels, Cinv, ldc, w, nullptr, dlogits, ldd);
     int rc = launch_status();
     if (rc) return rc;
     hipLaunchKernelGGL(k_bc_sum, dim3(1), dim3(256), 0, st, w, (int)B, (int)C, loss);
@@ -631,8 +554,7 @@ extern "C" int ngnn_bc_loss_bwd(const float *logits, int64_t ld, int64_t B, int6
                    NGNN_E_ARG);
     NGNN_RETURN_IF(ld < C || ldc < C || ldd < C, NGNN_E_SHAPE);
     NGNN_RETURN_IF(!fits_i32(B) || !fits_i32(C), NGNN_E_RANGE);
-    hipLaunchKernelGGL(k_bc_rows, dim3(static_cast<unsigned>(ceil_div(B, 4))), dim3(256), 0,
-                       as_stream(stream), logits, ld, (int)B, (int)C, labels, Cinv, ldc,
-                       static_cast<float *>(nullptr), grad_scale, dlogits, ldd);
+    launch_rows(k_bc_rows, B, as_stream(stream), logits, ld, (int)B, (int)C, labels, Cinv, ldc, nullptr,
+                grad_scale, dlogits, ldd);
     return launch_status();
 }

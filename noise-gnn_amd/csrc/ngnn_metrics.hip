@@ -22,7 +22,7 @@
 // vector atomics (the result does not depend on their order).
 #include <algorithm>
 
-#include "ngnn_internal.h"
+#include "ngnn_rows.h"
 
 namespace ngnn {
 namespace {
@@ -34,8 +34,9 @@ constexpr int kSplitThreads = 1024;
 
 typedef unsigned long long u64;
 
-// Monotone over the floats: -inf < ... < -0 == +0 < ... < +inf < NaN.
-__device__ __forceinline__ uint32_t order_key(float v) {
+// Monotone over the floats as torch.argmax compares them: -inf < ... < -0 ==
+// +0 < ... < +inf < NaN.  (ngnn_loss's loss_order_key keeps -0 below +0.)
+__device__ __forceinline__ uint32_t argmax_order_key(float v) {
     if (v != v) return 0xFFFFFFFFu;
     if (v == 0.0f) return 0x80000000u;
     const uint32_t b = __float_as_uint(v);
@@ -57,7 +58,7 @@ template <bool BF16>
 __device__ __forceinline__ int group_argmax(const void *logits, int64_t off, int C, int G, int gl) {
     u64 best = 0;
     for (int c = gl; c < C; c += G) {
-        const u64 k = (static_cast<u64>(order_key(load_elem<BF16>(logits, off + c))) << 32) |
+        const u64 k = (static_cast<u64>(argmax_order_key(load_elem<BF16>(logits, off + c))) << 32) |
                       (0xFFFFFFFFu - static_cast<uint32_t>(c));
         best = k > best ? k : best;
     }
@@ -66,11 +67,6 @@ __device__ __forceinline__ int group_argmax(const void *logits, int64_t off, int
         best = o > best ? o : best;
     }
     return static_cast<int>(0xFFFFFFFFu - static_cast<uint32_t>(best));
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-    for (int m = kWave >> 1; m > 0; m >>= 1) v += __shfl_xor(v, m);
-    return v;
 }
 
 // ------------------------------------------------------------ step metrics

@@ -18,19 +18,12 @@
 // otherwise.  The atomic pass is always one dword per lane over consecutive
 // addresses: a wave's instruction then covers whole 64..256-B segments, the
 // shape float atomics run at their full rate in.
-#include "ngnn_internal.h"
+#include "ngnn_rows.h"
 
 namespace ngnn {
 namespace {
 
 constexpr float kNormEps = 1e-12f;  // F.normalize's eps
-
-template <int LPR>
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-    for (int o = LPR / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 __device__ __forceinline__ float sign_of(float x) {
     return x > 0.0f ? 1.0f : (x < 0.0f ? -1.0f : 0.0f);

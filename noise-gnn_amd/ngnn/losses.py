@@ -9,9 +9,11 @@ the backward then costs nothing when its incoming gradient is the training
 step's persistent unit tensor (``unit_grad``, marked ``_ngnn_unit``) and one
 launch otherwise.  The input gradient is a view of a zero-initialised
 buffer whose rows >= batch_size stay zero (only rows < batch_size are ever
-written), and it tells the SAGE stack's backward how many leading rows can
-be nonzero (``_ngnn_nonzero_rows``), so that backward skips its row-extent
-scan.
+written), held by its node from the forward on (``_GradHold``: one pool of
+such buffers for every loss here, and the rule that keeps two nodes of one
+backward pass off the same storage), and it tells the SAGE stack's backward
+how many leading rows can be nonzero (``_ngnn_nonzero_rows``), so that
+backward skips its row-extent scan.
 
 The reference's other losses follow the same plan: ``CTLoss`` and
 ``CoDiLoss`` (ngnn_ct_loss_* / ngnn_codi_loss_*: both models' row losses,
@@ -32,10 +34,9 @@ import weakref
 import torch
 
 from . import _lib
+from ._common import device_counter, read_counter, rows_ld
 
-_zero_rows: dict = {}
 _ws: dict = {}
-_free_grads: dict = {}  # (dev, C, B) -> zero-row gradient buffers not held by a pending node
 
 
 def unit_grad(loss: torch.Tensor) -> torch.Tensor:
@@ -47,34 +48,52 @@ def unit_grad(loss: torch.Tensor) -> torch.Tensor:
     return one
 
 
-def _take_grad_buffer(dev, n: int, c: int, b: int) -> torch.Tensor:
-    """A zero-row [>= n, c] gradient buffer for ONE pending loss node: two
-    forwards before one backward (several losses per step) get different
-    buffers.  Returned to the pool by the node's backward (or when its graph
-    is freed without one)."""
-    key = (dev, c, b)
-    pool = _free_grads.setdefault(key, [])
-    while pool:
-        buf = pool.pop()
-        if buf.size(0) >= n:
-            return buf
-    return torch.zeros(max(n, 1), c, dtype=torch.float32, device=dev)
-
-
-def _give_back(key, buf) -> None:
-    _free_grads.setdefault(key, []).append(buf)
+# ---------------------------------------------------------------------------
+# The zero-row gradient pool.  Every loss here that reads only the B seed rows
+# of an [N, C] input returns its gradient as a view of a zero-initialised
+# buffer: only rows < B are ever written, so rows >= B are zero without a
+# fill.  THE RULE: a buffer returned as a gradient by one node is never handed
+# to another node that can run in the same backward pass -- autograd adds the
+# gradients that meet at one input, and two views of one storage would add up
+# to twice the last one written.  So
+#   - a node takes its buffer at FORWARD time (_GradHold), for the inputs that
+#     need a gradient: as many pending nodes, as many buffers;
+#   - it gives the buffer back at its first backward, or when its graph is
+#     dropped unused: steady state is one buffer per key, and stream order
+#     protects the rows until that backward pass has consumed them;
+#   - nothing is drawn from the free list at backward time: a node that is
+#     back-propagated again writes into a zero buffer of its own.
+_free_grads: dict = {}  # (device, C, tag, dtype) -> buffers no pending node holds
 
 
 class _GradHold:
-    """Owns a taken gradient buffer until backward hands it back (weakref
-    finalizer: also when the autograd graph is dropped unused)."""
+    """One pending node's [>= n, c] zero-row buffer.  `tag` tells the losses
+    and their B apart: a buffer shared with a larger B would hold that call's
+    stale rows in [B, B_larger)."""
 
-    def __init__(self, key, buf):
-        self.buf = buf
-        self._fin = weakref.finalize(self, _give_back, key, buf)
+    def __init__(self, dev, n: int, c: int, tag, dtype=torch.float32):
+        free = _free_grads.setdefault((dev, c, tag, dtype), [])
+        self.buf = None
+        while free and self.buf is None:
+            buf = free.pop()
+            if buf.size(0) >= n:  # (a shorter one is dropped: grown on demand)
+                self.buf = buf
+        if self.buf is None:
+            self.buf = torch.zeros(max(n, 1), c, dtype=dtype, device=dev)
+        # (weakref finalizer: also when the autograd graph is dropped unused)
+        self._pooled = weakref.finalize(self, free.append, self.buf)
+        self._own = None
 
-    def release(self):
-        self._fin()
+    def rows(self, n: int):
+        """``(buf[:n], first)`` for one backward of the holding node.  first:
+        the rows are as the forward left them, and the buffer goes back to
+        the pool.  Not first (retain_graph): a zero buffer this node owns."""
+        if self._pooled.alive:
+            self._pooled()
+            return self.buf[:n], True
+        if self._own is None:
+            self._own = torch.zeros_like(self.buf)
+        return self._own[:n], False
 
 
 def _workspace(dev, B: int) -> torch.Tensor:
@@ -89,113 +108,101 @@ def _workspace(dev, B: int) -> torch.Tensor:
     return buf
 
 
-def _grad_buffer(dev, n: int, c: int, b: int) -> torch.Tensor:
-    """[n, c] view of a cached zero-initialised buffer; only rows < b are
-    ever written, so rows >= b are zero.  Grown on demand (zeros).  One
-    buffer per (C, b): a buffer shared with a larger b would hold that
-    call's stale rows in [b, b_larger)."""
-    key = (dev, c, b)
-    buf = _zero_rows.get(key)
-    if buf is None or buf.size(0) < n:
-        buf = torch.zeros(max(n, 1), c, dtype=torch.float32, device=dev)
-        _zero_rows[key] = buf
-    return buf[:n]
+class _SeedRowLoss(torch.autograd.Function):
+    """The skeleton of an fp32 loss over the seed rows ``logits[:B]`` whose
+    forward launch also writes the unit-scale gradient rows: the hold, the
+    unit-gradient shortcut (no launch in backward) and the recompute for any
+    other gradient or a second backward.  A subclass gives ``tag`` and
+      _fwd(ctx, x, ld, yy, arg, loss, dx) -> the tensors its _bwd needs saved
+                                             (dx None: no gradient wanted)
+      _bwd(ctx, x, ld, yy, saved, g, dx)  -> rows < B of dx for the scalar g
+    where ``arg`` is the loss's one extra argument."""
 
-
-class _SeedXent(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, logits, y, batch_size: int, ignore_index: int):
-        B = int(batch_size)
-        x = logits if logits.stride(1) == 1 else logits.contiguous()
-        yy = y[:B].contiguous()
+    @classmethod
+    def forward(cls, ctx, logits, y, batch_size: int, arg):
+        ctx.B, ctx.n = int(batch_size), logits.size(0)
+        x, ctx.ld = rows_ld(logits)
+        yy = y[:ctx.B].contiguous()
         loss = torch.empty((), dtype=torch.float32, device=x.device)
-        count = torch.empty((), dtype=torch.float32, device=x.device)
-        ws = _workspace(x.device, B)
-        lib = _lib.load()
         ctx.hold = None
         if ctx.needs_input_grad[0]:
-            # loss + the unit-scale gradient in one launch
-            key = (x.device, x.size(1), B)
-            hold = _GradHold(key, _take_grad_buffer(x.device, logits.size(0), x.size(1), B))
-            dx = hold.buf
-            _lib.check(lib.ngnn_seed_xent_fwd_grad(
-                _lib.ptr(x), x.stride(0), B, x.size(1), _lib.ptr(yy), int(ignore_index),
-                _lib.ptr(loss), _lib.ptr(count), _lib.ptr(dx), dx.stride(0), _lib.ptr(ws),
-                ws.numel(), _lib.stream_handle(x.device)), "ngnn_seed_xent_fwd_grad")
-            ctx.hold = hold
-        else:
-            _lib.check(lib.ngnn_seed_xent_fwd(
-                _lib.ptr(x), x.stride(0), B, x.size(1), _lib.ptr(yy), int(ignore_index),
-                _lib.ptr(loss), _lib.ptr(count), _lib.ptr(ws), ws.numel(),
-                _lib.stream_handle(x.device)), "ngnn_seed_xent_fwd")
-        ctx.ws = ws
-        ctx.save_for_backward(x, yy, count)
-        ctx.B, ctx.ignore, ctx.n = B, int(ignore_index), logits.size(0)
+            ctx.hold = _GradHold(x.device, ctx.n, x.size(1), (cls.tag, ctx.B))
+        saved = cls._fwd(ctx, x, ctx.ld, yy, arg, loss, None if ctx.hold is None else ctx.hold.buf)
+        ctx.save_for_backward(x, yy, *saved)
         return loss
 
-    @staticmethod
-    def backward(ctx, g):
-        x, yy, count = ctx.saved_tensors
-        hold = ctx.hold
-        if hold is not None:
-            # the gradient rows the forward wrote (unit scale); the buffer goes
-            # back to the pool -- stream order protects it until its consumer
-            # (this backward pass) has read it
-            dx = hold.buf[:ctx.n]
-            ctx.hold = None
-            hold.release()
-            if getattr(g, "_ngnn_unit", False):
-                dx._ngnn_nonzero_rows = ctx.B  # rows >= B are zero: the SAGE backward's row bound
-                return dx, None, None, None
-        else:
-            dx = _grad_buffer(x.device, ctx.n, x.size(1), ctx.B)
-        g = g.contiguous()
-        _lib.check(_lib.load().ngnn_seed_xent_bwd(
-            _lib.ptr(x), x.stride(0), ctx.B, x.size(1), _lib.ptr(yy), ctx.ignore, _lib.ptr(ctx.ws),
-            _lib.ptr(g), _lib.ptr(count), _lib.ptr(dx), dx.stride(0), _lib.stream_handle(x.device)),
-            "ngnn_seed_xent_bwd")
+    @classmethod
+    def backward(cls, ctx, g):
+        x, yy, *saved = ctx.saved_tensors
+        dx, first = ctx.hold.rows(ctx.n)
+        if not (first and getattr(g, "_ngnn_unit", False)):
+            cls._bwd(ctx, x, ctx.ld, yy, saved, g, dx)
         dx._ngnn_nonzero_rows = ctx.B  # rows >= B are zero: the SAGE backward's row bound
         return dx, None, None, None
 
 
-_bf16_rows: dict = {}
+def _seed_xent_bwd(x, ld, B, yy, ignore, ws, g, count, dx) -> None:
+    g = g.contiguous()
+    _lib.check(_lib.load().ngnn_seed_xent_bwd(
+        _lib.ptr(x), ld, B, x.size(1), _lib.ptr(yy), ignore, _lib.ptr(ws), _lib.ptr(g), _lib.ptr(count),
+        _lib.ptr(dx), dx.stride(0), _lib.stream_handle(x.device)), "ngnn_seed_xent_bwd")
 
 
-class _SeedXentBF16(torch.autograd.Function):
-    """seed_cross_entropy of bf16 logits: only rows < B are widened (B x C, not
-    the N x C logits), the fp32 kernels run on them, and the gradient comes
-    back as bf16 [N, C] with rows >= B zero (a cached buffer, like the fp32
-    path's) carrying the row hint."""
+class _SeedXent(_SeedRowLoss):
+    tag = "xent"
 
     @staticmethod
-    def forward(ctx, logits, y, batch_size: int, ignore_index: int):
+    def _fwd(ctx, x, ld, yy, ignore_index, loss, dx):
+        count = torch.empty((), dtype=torch.float32, device=x.device)
+        ctx.ws, ctx.ignore = _workspace(x.device, ctx.B), int(ignore_index)
+        lib, ws = _lib.load(), ctx.ws
+        if dx is not None:  # loss + the unit-scale gradient in one launch
+            _lib.check(lib.ngnn_seed_xent_fwd_grad(
+                _lib.ptr(x), ld, ctx.B, x.size(1), _lib.ptr(yy), ctx.ignore, _lib.ptr(loss), _lib.ptr(count),
+                _lib.ptr(dx), dx.stride(0), _lib.ptr(ws), ws.numel(), _lib.stream_handle(x.device)),
+                "ngnn_seed_xent_fwd_grad")
+        else:
+            _lib.check(lib.ngnn_seed_xent_fwd(
+                _lib.ptr(x), ld, ctx.B, x.size(1), _lib.ptr(yy), ctx.ignore, _lib.ptr(loss), _lib.ptr(count),
+                _lib.ptr(ws), ws.numel(), _lib.stream_handle(x.device)), "ngnn_seed_xent_fwd")
+        return (count,)
+
+    @staticmethod
+    def _bwd(ctx, x, ld, yy, saved, g, dx):
+        _seed_xent_bwd(x, ld, ctx.B, yy, ctx.ignore, ctx.ws, g, saved[0], dx)
+
+
+class _BF16SeedRows(torch.autograd.Function):
+    """A seed-row loss (``node``: _SeedXent or _BCLoss) of bf16 logits: only
+    rows < B are widened (B x C, not the N x C logits), the fp32 node runs on
+    them, and the gradient comes back as bf16 [N, C] with rows >= B zero (a
+    pooled buffer of its own, like the fp32 node's) carrying the row hint."""
+
+    @staticmethod
+    def forward(ctx, logits, y, batch_size: int, arg, node):
         B = int(batch_size)
-        ctx.n_full = logits.size(0)
+        ctx.node, ctx.n_full = node, logits.size(0)
+        ctx.out_hold = None
+        if ctx.needs_input_grad[0]:
+            ctx.out_hold = _GradHold(logits.device, ctx.n_full, logits.size(1), (node.tag, B), torch.bfloat16)
         # the seed rows widened by the library (exact; an ATen copy kernel
         # otherwise), then the fp32 node's forward on them (it fills ctx for
-        # its backward: saved rows, ws, B, n = B)
-        lw = logits if logits.stride(1) == 1 else logits.contiguous()
+        # its backward: saved rows, B, n = B)
+        lw, ld = rows_ld(logits)
         wide = torch.empty(B, lw.size(1), dtype=torch.float32, device=lw.device)
-        _lib.check(_lib.load().ngnn_widen_bf16_rows(_lib.ptr(lw), lw.stride(0), lw.size(1), B, None,
-                                                    _lib.ptr(wide), wide.stride(0),
-                                                    _lib.stream_handle(lw.device)), "ngnn_widen_bf16_rows")
-        return _SeedXent.forward(ctx, wide, y, B, ignore_index)
+        _lib.check(_lib.load().ngnn_widen_bf16_rows(_lib.ptr(lw), ld, lw.size(1), B, None, _lib.ptr(wide),
+                                                    wide.stride(0), _lib.stream_handle(lw.device)),
+                   "ngnn_widen_bf16_rows")
+        return node.forward(ctx, wide, y, B, arg)
 
     @staticmethod
     def backward(ctx, g):
-        dx, _, _, _ = _SeedXent.backward(ctx, g)  # fp32 [B, C] (ctx.n == B there)
-        n, B, C = ctx.n_full, ctx.B, dx.size(1)
-        key = (dx.device, C, B, "bf16")
-        buf = _bf16_rows.get(key)
-        if buf is None or buf.size(0) < n:
-            buf = torch.zeros(max(n, 1), C, dtype=torch.bfloat16, device=dx.device)
-            _bf16_rows[key] = buf
-        out = buf[:n]
-        d = dx[:B] if dx[:B].is_contiguous() else dx[:B].contiguous()
-        _lib.check(_lib.load().ngnn_cast_f32_bf16(_lib.ptr(d), _lib.ptr(out), B * C,
-                                                  _lib.stream_handle(d.device)), "ngnn_cast_f32_bf16")
-        out._ngnn_nonzero_rows = B
-        return out, None, None, None
+        dx = ctx.node.backward(ctx, g)[0]  # fp32 [B, C], contiguous (ctx.n == B there)
+        out, _ = ctx.out_hold.rows(ctx.n_full)
+        _lib.check(_lib.load().ngnn_cast_f32_bf16(_lib.ptr(dx), _lib.ptr(out), dx.numel(),
+                                                  _lib.stream_handle(dx.device)), "ngnn_cast_f32_bf16")
+        out._ngnn_nonzero_rows = ctx.B
+        return out, None, None, None, None
 
 
 class _CastKeepRows(torch.autograd.Function):
@@ -246,13 +253,12 @@ class _HeadXent(torch.autograd.Function):
             dy._ngnn_g_pre = hd.g
             return dy, None
         (x,) = ctx.saved_tensors
-        dx = _grad_buffer(x.device, ctx.n, x.size(1), hd.B)
-        yy = hd.y[:hd.B]
-        g = g.contiguous()
-        _lib.check(_lib.load().ngnn_seed_xent_bwd(
-            _lib.ptr(x), x.stride(0), hd.B, x.size(1), _lib.ptr(yy), hd.ignore, _lib.ptr(hd.ws),
-            _lib.ptr(g), _lib.ptr(res.count), _lib.ptr(dx), dx.stride(0), _lib.stream_handle(x.device)),
-            "ngnn_seed_xent_bwd")
+        # a zero-row buffer kept on the head (one pending node per slot), never
+        # the pool's: nothing is drawn from the free list at backward time
+        if getattr(hd, "dy_scaled", None) is None:
+            hd.dy_scaled = torch.zeros_like(hd.dy)
+        dx = hd.dy_scaled[:ctx.n]
+        _seed_xent_bwd(x, x.stride(0), hd.B, hd.y[:hd.B], hd.ignore, hd.ws, g, res.count, dx)
         dx._ngnn_nonzero_rows = hd.B
         return dx, None
 
@@ -271,7 +277,7 @@ def seed_cross_entropy(logits: torch.Tensor, y: torch.Tensor, batch_size: int,
         return _HeadXent.apply(logits, res)
     if logits.dtype == torch.bfloat16:  # bf16 models: the loss is taken in fp32
         if logits.dim() == 2 and 0 < batch_size <= logits.size(0) and y.numel() >= batch_size:
-            return _SeedXentBF16.apply(logits, y, batch_size, ignore_index)
+            return _BF16SeedRows.apply(logits, y, batch_size, ignore_index, _SeedXent)
         logits = cast_keep_rows(logits, torch.float32)
     if logits.dim() != 2 or logits.dtype != torch.float32:
         raise ValueError("logits must be a 2-D float32 (or bf16) tensor")
@@ -295,13 +301,16 @@ class _CTPick(torch.autograd.Function):
     function of y_m alone, so that loss_1.backward() and loss_2.backward()
     each run only their own model's graph, as in pipeline.py:125-131.
     y_m may hold more rows than the loss reads (the whole block's logits,
-    CTLoss(..., batch_size=B)): its gradient is then a zero-row buffer whose
-    rows < B the backward launch writes (no slice backward), marked for the
-    SAGE stack's bounded backward."""
+    CTLoss(..., batch_size=B)): its gradient is then a pooled zero-row buffer,
+    taken here at forward time, whose rows < B the backward launch writes (no
+    slice backward), marked for the SAGE stack's bounded backward."""
 
     @staticmethod
     def forward(ctx, y, state: _CTState, m: int):
         ctx.state, ctx.m, ctx.n = state, m, y.size(0)
+        ctx.hold = None
+        if ctx.n > state.B and ctx.needs_input_grad[0]:  # rows >= B never written: zero
+            ctx.hold = _GradHold(y.device, ctx.n, state.C, ("ct", state.B))
         ctx.save_for_backward(y)
         return state.out[m].clone()
 
@@ -309,13 +318,13 @@ class _CTPick(torch.autograd.Function):
     def backward(ctx, g):
         (y,) = ctx.saved_tensors
         st = ctx.state
-        if ctx.n > st.B:  # rows >= B never written: zero (one buffer per model)
-            dy = _grad_buffer(y.device, ctx.n, st.C, ("ct", ctx.m, st.B))
+        if ctx.hold is not None:
+            dy, _ = ctx.hold.rows(ctx.n)
         else:
             dy = torch.empty(st.B, st.C, dtype=torch.float32, device=y.device)
         g = g.reshape(1).to(torch.float32).contiguous()
         _lib.check(_lib.load().ngnn_ct_loss_bwd(
-            ctx.m, _lib.ptr(y), y.stride(0), st.B, st.C, _lib.ptr(st.y_noise), st.ignore,
+            ctx.m, _lib.ptr(y), rows_ld(y)[1], st.B, st.C, _lib.ptr(st.y_noise), st.ignore,
             _lib.ptr(st.ws), _lib.ptr(g), _lib.ptr(dy), dy.stride(0),
             _lib.stream_handle(y.device)), "ngnn_ct_loss_bwd")
         dy._ngnn_nonzero_rows = st.B
@@ -381,8 +390,7 @@ def _exchange_forward(name, ignore_index, co_lambda, y_1, y_2, y_noise, forget_r
     num_remember = int(remember_rate * B)  # losses.py:29-30, same float arithmetic
     if not 0 <= num_remember <= B:
         raise ValueError(f"forget_rate {forget_rate} gives num_remember {num_remember}")
-    a = y_1 if y_1.stride(1) == 1 else y_1.contiguous()
-    b = y_2 if y_2.stride(1) == 1 else y_2.contiguous()
+    (a, lda), (b, ldb) = rows_ld(y_1), rows_ld(y_2)
     yn = y_noise.to(device=dev, dtype=torch.int64).reshape(-1)
     if batch_size is not None:  # (a block's labels / ids: the seed rows')
         yn = yn[:B]
@@ -403,14 +411,14 @@ def _exchange_forward(name, ignore_index, co_lambda, y_1, y_2, y_noise, forget_r
     if co_lambda is None:
         ws = torch.empty(lib.ngnn_ct_loss_workspace_bytes(B), dtype=torch.uint8, device=dev)
         _lib.check(lib.ngnn_ct_loss_fwd(
-            _lib.ptr(a), a.stride(0), _lib.ptr(b), b.stride(0), B, C, _lib.ptr(yn),
+            _lib.ptr(a), lda, _lib.ptr(b), ldb, B, C, _lib.ptr(yn),
             int(ignore_index), num_remember, _lib.ptr(idx), _lib.ptr(clean),
             0 if clean is None else clean.numel(), _lib.ptr(out), _lib.ptr(i1), _lib.ptr(i2),
             _lib.ptr(ws), ws.numel(), _lib.ptr(err), _lib.stream_handle(dev)), "ngnn_ct_loss_fwd")
     else:
         ws = torch.empty(lib.ngnn_codi_loss_workspace_bytes(B), dtype=torch.uint8, device=dev)
         _lib.check(lib.ngnn_codi_loss_fwd(
-            _lib.ptr(a), a.stride(0), _lib.ptr(b), b.stride(0), B, C, _lib.ptr(yn),
+            _lib.ptr(a), lda, _lib.ptr(b), ldb, B, C, _lib.ptr(yn),
             int(ignore_index), num_remember, float(co_lambda), _lib.ptr(idx), _lib.ptr(clean),
             0 if clean is None else clean.numel(), _lib.ptr(out), _lib.ptr(i1), _lib.ptr(i2), None,
             _lib.ptr(ws), ws.numel(), _lib.ptr(err), _lib.stream_handle(dev)), "ngnn_codi_loss_fwd")
@@ -492,83 +500,26 @@ def _correction_inverse(C, dev) -> torch.Tensor:
     return inv
 
 
-class _BCLoss(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, logits, y, cinv, batch_size: int):
-        B = int(batch_size)
-        x = logits if logits.stride(1) == 1 else logits.contiguous()
-        yy = y[:B].contiguous()
-        loss = torch.empty((), dtype=torch.float32, device=x.device)
-        lib = _lib.load()
-        ws = torch.empty(lib.ngnn_bc_loss_workspace_bytes(B), dtype=torch.uint8, device=x.device)
-        dx, ctx.hold = None, None
-        if ctx.needs_input_grad[0]:
-            # loss + the unit-scale gradient rows in the same launch
-            key = (x.device, x.size(1), ("bc", B))
-            ctx.hold = _GradHold(key, _take_grad_buffer(x.device, logits.size(0), x.size(1), ("bc", B)))
-            dx = ctx.hold.buf
-        _lib.check(lib.ngnn_bc_loss_fwd(
-            _lib.ptr(x), x.stride(0), B, x.size(1), _lib.ptr(yy), _lib.ptr(cinv), cinv.stride(0),
-            _lib.ptr(loss), _lib.ptr(dx), 0 if dx is None else dx.stride(0), _lib.ptr(ws), ws.numel(),
-            _lib.stream_handle(x.device)), "ngnn_bc_loss_fwd")
-        ctx.save_for_backward(x, yy, cinv)
-        ctx.B, ctx.n = B, logits.size(0)
-        return loss
+class _BCLoss(_SeedRowLoss):
+    tag = "bc"
 
     @staticmethod
-    def backward(ctx, g):
-        x, yy, cinv = ctx.saved_tensors
-        hold = ctx.hold
-        if hold is not None:
-            # (as _SeedXent: stream order protects the pooled buffer until this
-            # backward pass has read it)
-            dx = hold.buf[:ctx.n]
-            ctx.hold = None
-            hold.release()
-            if getattr(g, "_ngnn_unit", False):
-                dx._ngnn_nonzero_rows = ctx.B
-                return dx, None, None, None
-        else:
-            dx = _grad_buffer(x.device, ctx.n, x.size(1), ("bc", ctx.B))
+    def _fwd(ctx, x, ld, yy, cinv, loss, dx):
+        lib = _lib.load()
+        ws = torch.empty(lib.ngnn_bc_loss_workspace_bytes(ctx.B), dtype=torch.uint8, device=x.device)
+        _lib.check(lib.ngnn_bc_loss_fwd(
+            _lib.ptr(x), ld, ctx.B, x.size(1), _lib.ptr(yy), _lib.ptr(cinv), cinv.stride(0), _lib.ptr(loss),
+            _lib.ptr(dx), 0 if dx is None else dx.stride(0), _lib.ptr(ws), ws.numel(),
+            _lib.stream_handle(x.device)), "ngnn_bc_loss_fwd")
+        return (cinv,)
+
+    @staticmethod
+    def _bwd(ctx, x, ld, yy, saved, g, dx):
+        (cinv,) = saved
         g = g.reshape(1).to(torch.float32).contiguous()
         _lib.check(_lib.load().ngnn_bc_loss_bwd(
-            _lib.ptr(x), x.stride(0), ctx.B, x.size(1), _lib.ptr(yy), _lib.ptr(cinv), cinv.stride(0),
-            _lib.ptr(g), _lib.ptr(dx), dx.stride(0), _lib.stream_handle(x.device)), "ngnn_bc_loss_bwd")
-        dx._ngnn_nonzero_rows = ctx.B
-        return dx, None, None, None
-
-
-class _BCLossBF16(torch.autograd.Function):
-    """backward_correction of bf16 logits, as _SeedXentBF16: the seed rows
-    widened, the fp32 kernels on them, the gradient bf16 [N, C] with rows >= B
-    zero, carrying the row hint."""
-
-    @staticmethod
-    def forward(ctx, logits, y, cinv, batch_size: int):
-        B = int(batch_size)
-        ctx.n_full = logits.size(0)
-        lw = logits if logits.stride(1) == 1 else logits.contiguous()
-        wide = torch.empty(B, lw.size(1), dtype=torch.float32, device=lw.device)
-        _lib.check(_lib.load().ngnn_widen_bf16_rows(_lib.ptr(lw), lw.stride(0), lw.size(1), B, None,
-                                                    _lib.ptr(wide), wide.stride(0),
-                                                    _lib.stream_handle(lw.device)), "ngnn_widen_bf16_rows")
-        return _BCLoss.forward(ctx, wide, y, cinv, B)
-
-    @staticmethod
-    def backward(ctx, g):
-        dx, _, _, _ = _BCLoss.backward(ctx, g)  # fp32 [B, C] (ctx.n == B there)
-        n, B, C = ctx.n_full, ctx.B, dx.size(1)
-        key = (dx.device, C, B, "bc-bf16")
-        buf = _bf16_rows.get(key)
-        if buf is None or buf.size(0) < n:
-            buf = torch.zeros(max(n, 1), C, dtype=torch.bfloat16, device=dx.device)
-            _bf16_rows[key] = buf
-        out = buf[:n]
-        d = dx[:B] if dx[:B].is_contiguous() else dx[:B].contiguous()
-        _lib.check(_lib.load().ngnn_cast_f32_bf16(_lib.ptr(d), _lib.ptr(out), B * C,
-                                                  _lib.stream_handle(d.device)), "ngnn_cast_f32_bf16")
-        out._ngnn_nonzero_rows = B
-        return out, None, None, None
+            _lib.ptr(x), ld, ctx.B, x.size(1), _lib.ptr(yy), _lib.ptr(cinv), cinv.stride(0), _lib.ptr(g),
+            _lib.ptr(dx), dx.stride(0), _lib.stream_handle(x.device)), "ngnn_bc_loss_bwd")
 
 
 def backward_correction(output: torch.Tensor, labels: torch.Tensor, C, nbr_class: int, device=None,
@@ -599,35 +550,21 @@ def backward_correction(output: torch.Tensor, labels: torch.Tensor, C, nbr_class
         raise ValueError("labels must hold one label per row")
     cinv = _correction_inverse(C, output.device)
     y = labels.to(device=output.device, dtype=torch.int64)
-    fn = _BCLossBF16 if output.dtype == torch.bfloat16 else _BCLoss
-    return fn.apply(output, y, cinv, B)
+    if output.dtype == torch.bfloat16:
+        return _BF16SeedRows.apply(output, y, B, cinv, _BCLoss)
+    return _BCLoss.apply(output, y, B, cinv)
 
 
 # ---------------------------------------------------------------------------
 # Contrastive discriminator loss (Discriminator_innerprod + BCEExeprtLoss,
 # src/utils/data_utils.py:34-64)
 
-_bad_index_counters: dict = {}  # device index -> int32[1] on that device
-
-
-def _bad_index_counter(device: torch.device) -> torch.Tensor:
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    c = _bad_index_counters.get(idx)
-    if c is None:
-        c = _bad_index_counters[idx] = torch.zeros(1, dtype=torch.int32, device=torch.device("cuda", idx))
-    return c
-
-
 def contrast_bad_indices(device=None, reset: bool = False) -> int:
     """How many ``index`` entries ``contrastive_loss`` met on ``device`` outside
     its rows (each makes that call's loss NaN).  Debugging only: reading the
     device counter synchronises (``contrastive_loss.bad_index`` is the counter
     itself, a device tensor)."""
-    c = _bad_index_counter(torch.device("cuda" if device is None else device))
-    n = int(c.item())
-    if reset:
-        c.zero_()
-    return n
+    return read_counter("bad-index", device, "contrastive_loss", reset)
 
 
 class _Contrast(torch.autograd.Function):
@@ -646,17 +583,16 @@ class _Contrast(torch.autograd.Function):
         lib = _lib.load()
         out = torch.empty(3, dtype=torch.float32, device=dev)
         ws = torch.empty(lib.ngnn_contrast_workspace_bytes(M), dtype=torch.uint8, device=dev)
-        bad = _bad_index_counter(dev)
+        bad = device_counter("bad-index", dev, "contrastive_loss")
         _lib.check(lib.ngnn_contrast_fwd(
             _lib.ptr(h), h.stride(0), _lib.ptr(hp), hp.stride(0), _lib.ptr(hn), hn.stride(0), rows, H,
             _lib.ptr(index), M, _lib.ptr(out), _lib.ptr(bad), _lib.ptr(ws), ws.numel(),
             _lib.stream_handle(dev)), "ngnn_contrast_fwd")
         ctx.holds = [None, None, None]
         if B is not None:
-            key = (dev, H, ("contrast", B))
             for k in range(3):
                 if ctx.needs_input_grad[k]:
-                    ctx.holds[k] = _GradHold(key, _take_grad_buffer(dev, N, H, ("contrast", B)))
+                    ctx.holds[k] = _GradHold(dev, N, H, ("contrast", B))
         ctx.save_for_backward(h, hp, hn, index)
         ctx.ws, ctx.B, ctx.rows = ws, B, rows
         return out[0].clone()
@@ -674,11 +610,7 @@ class _Contrast(torch.autograd.Function):
             if hold is None:
                 grads[k] = torch.zeros(N, H, dtype=torch.float32, device=dev)
             else:
-                # back to the pool: stream order protects the rows until this
-                # backward pass has consumed them (as _SeedXent)
-                d = hold.buf[:N]
-                ctx.holds[k] = None
-                hold.release()
+                d, _ = hold.rows(N)
                 d[:ctx.B].zero_()
                 d._ngnn_nonzero_rows = ctx.B  # rows >= B are zero: the SAGE backward's row bound
                 grads[k] = d
@@ -728,13 +660,15 @@ def contrastive_loss(h: torch.Tensor, h_pos: torch.Tensor, h_neg: torch.Tensor, 
         batch_size = int(batch_size)
         if not 0 < batch_size <= N:
             raise ValueError(f"batch_size {batch_size} outside (0, {N}]")
-    contrastive_loss.bad_index = _bad_index_counter(h.device)
+    contrastive_loss.bad_index = device_counter("bad-index", h.device, "contrastive_loss")
     index = index.reshape(-1).contiguous()
     if H == 0:
         raise ValueError("contrastive_loss: H must be positive")
     if index.numel() == 0:  # (the entries refuse M == 0)
         return torch.full((), float("nan"), dtype=torch.float32, device=h.device)
-    a, p, n = (t if t.stride(1) == 1 and t.stride(0) >= H else t.contiguous() for t in (h, h_pos, h_neg))
+    # stricter than rows_ld alone: a single row with a short stride is copied
+    # too, so that _Contrast can pass stride(0) as every operand's ld
+    a, p, n = (rows_ld(t if t.stride(0) >= H else t.contiguous())[0] for t in (h, h_pos, h_neg))
     return _Contrast.apply(a, p, n, index, batch_size)
 
 
@@ -809,9 +743,7 @@ def get_uncertainty_batch(edge_index, y_pure: torch.Tensor, nbr_classes: int, de
         raise ValueError(f"get_uncertainty_batch: nbr_classes {nbr_classes} < 2")
     if y_pure.dim() != 2 or y_pure.dtype != torch.float32:
         raise ValueError("y_pure must be a 2-D float32 tensor")
-    y = y_pure.detach()
-    if y.size(1) and y.stride(1) != 1:
-        y = y.contiguous()
+    y, ld = rows_ld(y_pure.detach())
     N, C = y.shape
     blk = get_block(edge_index, N)
     if blk.n_src != N or blk.n_dst != N:
@@ -823,15 +755,10 @@ def get_uncertainty_batch(edge_index, y_pure: torch.Tensor, nbr_classes: int, de
     if R:
         csr = blk.transposed()
         _lib.check(_lib.load().ngnn_nbr_uncertainty(
-            _lib.ptr(y), y.stride(0) if N > 1 else max(C, 1), N, C, _lib.ptr(csr.rowptr), _lib.ptr(csr.col),
+            _lib.ptr(y), ld, N, C, _lib.ptr(csr.rowptr), _lib.ptr(csr.col),
             R, int(nbr_classes), float(epsilon), _lib.ptr(w), _lib.stream_handle(y.device)),
             "ngnn_nbr_uncertainty")
     return w
-
-
-def _ld(t: torch.Tensor) -> int:
-    """Row stride of a [B, C] view (a single row's stride is arbitrary)."""
-    return t.stride(0) if t.size(0) > 1 else max(t.stride(0), t.size(1))
 
 
 _FIX_CR_MODES = {("ce", True): 0, ("ce", False): 1, ("l2", True): 2, ("l2", False): 2}
@@ -849,6 +776,7 @@ class _FixCR(torch.autograd.Function):
     def forward(ctx, yp, yn, w, mode: int, p_cutoff: float):
         B, C = yp.shape
         dev = yp.device
+        ctx.ld = rows_ld(yp)[1], rows_ld(yn)[1]  # (fix_cr passed both through rows_ld: no copy here)
         lib = _lib.load()
         loss = torch.empty((), dtype=torch.float32, device=dev)
         ws = torch.empty(lib.ngnn_fix_cr_workspace_bytes(B), dtype=torch.uint8, device=dev)
@@ -856,7 +784,7 @@ class _FixCR(torch.autograd.Function):
         dp = torch.empty(B, C, dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] and mode else None
         dn = torch.empty(B, C, dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
         _lib.check(lib.ngnn_fix_cr_fwd(
-            _lib.ptr(yp), _ld(yp), _lib.ptr(yn), _ld(yn), B, C, mode, p_cutoff, _lib.ptr(w),
+            _lib.ptr(yp), ctx.ld[0], _lib.ptr(yn), ctx.ld[1], B, C, mode, p_cutoff, _lib.ptr(w),
             _lib.ptr(loss), _lib.ptr(dp), C, _lib.ptr(dn), C, _lib.ptr(ws), ws.numel(),
             _lib.stream_handle(dev)), "ngnn_fix_cr_fwd")
         ctx.save_for_backward(yp, yn, w)
@@ -877,7 +805,7 @@ class _FixCR(torch.autograd.Function):
         if fresh or not getattr(g, "_ngnn_unit", False):
             g = g.reshape(1).to(torch.float32).contiguous()
             _lib.check(_lib.load().ngnn_fix_cr_bwd(
-                _lib.ptr(yp), _ld(yp), _lib.ptr(yn), _ld(yn), B, C, ctx.mode, ctx.p_cutoff,
+                _lib.ptr(yp), ctx.ld[0], _lib.ptr(yn), ctx.ld[1], B, C, ctx.mode, ctx.p_cutoff,
                 _lib.ptr(w), _lib.ptr(g), _lib.ptr(dp), C, _lib.ptr(dn), C,
                 _lib.stream_handle(yp.device)), "ngnn_fix_cr_bwd")
         return dp, dn, None, None, None
@@ -915,11 +843,7 @@ def fix_cr(y_pure: torch.Tensor, y_noisy: torch.Tensor, ind_noisy=None, batch_si
     if B <= 0 or y_pure.size(1) == 0:
         raise ValueError("fix_cr: no rows or no classes")
     mode = _FIX_CR_MODES[(name, bool(use_hard_labels))]
-    yp, yn = y_pure[:B], y_noisy[:B]
-    if yp.stride(1) != 1:
-        yp = yp.contiguous()
-    if yn.stride(1) != 1:
-        yn = yn.contiguous()
+    yp, yn = rows_ld(y_pure[:B])[0], rows_ld(y_noisy[:B])[0]
     wb = None
     if w is not None and mode != 2:
         if not w.is_cuda:

@@ -19,6 +19,7 @@ import weakref
 import torch
 
 from . import _lib, _timing
+from ._common import rows_ld
 
 MAX_SCALARS = 4
 MAX_SEGMENTS = 8
@@ -41,18 +42,15 @@ def _dtype_code(t: torch.Tensor, what: str) -> int:
     raise TypeError(f"{what}: logits must be float32 or bfloat16, got {t.dtype}")
 
 
-def _logits_2d(t, what: str) -> torch.Tensor:
+def _logits_2d(t, what: str) -> tuple[torch.Tensor, int]:
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{what}: logits must be a torch tensor")
     if not t.is_cuda:
         raise RuntimeError(f"ngnn runs on the GPU only: {what}'s logits are on the CPU")
     if t.dim() != 2 or t.size(1) < 1:
         raise ValueError(f"{what}: logits must be [rows, C] with C >= 1, got shape {tuple(t.shape)}")
-    t = t.detach()
     # (rows of a column slice or of a padded buffer are read in place: only the columns must be dense)
-    if (t.size(1) > 1 and t.stride(1) != 1) or (t.size(0) > 1 and t.stride(0) < t.size(1)):
-        t = t.contiguous()
-    return t
+    return rows_ld(t.detach())
 
 
 def _labels_1d(y, dev, what: str) -> torch.Tensor:
@@ -111,7 +109,7 @@ class EpochMeter:
         ``y[:batch_size]`` (``[>= B]`` or ``[>= B, 1]``; ``batch_size=None``:
         all of ``y``), and one device scalar (a one-element float tensor, or
         ``None``) per name.  Returns ``None``; nothing is read on the host."""
-        lg = _logits_2d(logits, "EpochMeter.update")
+        lg, ld = _logits_2d(logits, "EpochMeter.update")
         dev = lg.device
         if dev != self.device:
             raise ValueError(f"EpochMeter.update: logits are on {dev}, the meter on {self.device}")
@@ -139,7 +137,6 @@ class EpochMeter:
             keep.append(s)
             ptrs[k] = s.data_ptr()
         C = lg.size(1)
-        ld = lg.stride(0) if lg.size(0) > 1 else C
         with _timing.span("step_metrics", B * (C * lg.element_size() + 8) + 64):
             rc = _lib.load().ngnn_step_metrics(_lib.ptr(lg), ld, _dtype_code(lg, "EpochMeter.update"), B, C,
                                                _lib.ptr(yy), int(ignore_index), ptrs[0], ptrs[1], ptrs[2], ptrs[3],
@@ -225,7 +222,7 @@ def split_accuracy(out, y, split_idx=None, *, return_pred: bool = False, confusi
     An index outside ``[0, N)``, or a label outside ``[0, C)`` that is not
     ``ignore_index``, raises ``ValueError`` naming the split (the reference
     raises ``IndexError``); such a row is never read."""
-    lg = _logits_2d(out, "split_accuracy")
+    lg, ld = _logits_2d(out, "split_accuracy")
     dev = lg.device
     yy = _labels_1d(y, dev, "split_accuracy")
     N, C = lg.shape
@@ -245,7 +242,6 @@ def split_accuracy(out, y, split_idx=None, *, return_pred: bool = False, confusi
     pred = torch.empty(M, dtype=torch.int64, device=dev) if return_pred else None
     conf = torch.empty(C, C, dtype=torch.int64, device=dev) if confusion else None
     host_bounds = (ctypes.c_int64 * (S + 1))(*bounds)
-    ld = lg.stride(0) if N > 1 else C
     with _timing.span("split_accuracy", M * (C * lg.element_size() + 16 + (8 if return_pred else 0))):
         rc = _lib.load().ngnn_split_accuracy(_lib.ptr(lg), ld, _dtype_code(lg, "split_accuracy"), N, C, _lib.ptr(yy),
                                              int(ignore_index), _lib.ptr(rows), M, S, host_bounds,

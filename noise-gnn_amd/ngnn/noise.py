@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib, _timing
+from ._common import device_counter, read_counter
 
 NOISE_TYPES = ("sym", "next_pair", "rand_pair", "aim_pair")
 # the launch geometry include/ngnn.h documents for ngnn_flip_labels
@@ -114,27 +115,12 @@ def _device_table(M: np.ndarray, dev: torch.device) -> torch.Tensor:
     return tab
 
 
-_bad_label_counters: dict = {}  # device index -> int32[1] on that device
-
-
-def _bad_label_counter(device: torch.device) -> torch.Tensor:
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    c = _bad_label_counters.get(idx)
-    if c is None:
-        c = _bad_label_counters[idx] = torch.zeros(1, dtype=torch.int32, device=torch.device("cuda", idx))
-    return c
-
-
 def label_noise_bad_labels(device=None, reset: bool = False) -> int:
     """How many labels ``flip_label`` met on ``device`` outside ``[0,
     nbr_classes)`` (each is copied unchanged; the reference raises an
     ``IndexError``).  Debugging only: reading the device counter
     synchronises."""
-    c = _bad_label_counter(torch.device("cuda" if device is None else device))
-    n = int(c.item())
-    if reset:
-        c.zero_()
-    return n
+    return read_counter("bad-label", device, "flip_label", reset)
 
 
 def max_classes() -> int:
@@ -207,7 +193,7 @@ def flip_label(labels: torch.Tensor, nbr_classes: int, noise_type: str = "sym", 
     if seed is None:
         seed = int(torch.randint(0, 1 << 62, (1,)).item())
     tab = _device_table(Mc, dev)
-    bad = _bad_label_counter(dev)
+    bad = device_counter("bad-label", dev, "flip_label")
     clean = counts = None
     if return_stats:
         clean = torch.empty(N, dtype=torch.bool, device=dev)

@@ -16,6 +16,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib, _timing
+from ._common import device_counter, read_counter, rows_ld
 from .block import Block
 
 
@@ -106,60 +107,29 @@ def sample_seed_rows(graph, fanout: int, batch_size: int, seed0: int, seed_strid
 
 # ---- SAGEPL's per-node input noise (ngnn_node_noise_fwd / _bwd) ----
 
-_bad_id_counters: dict = {}  # device index -> int32[1] on that device
-
-
-def _bad_id_counter(device: torch.device) -> torch.Tensor:
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    c = _bad_id_counters.get(idx)
-    if c is None:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("add_node_noise: call it once eagerly on this device before capturing "
-                               "(its bad-id counter is allocated at the first call)")
-        c = _bad_id_counters[idx] = torch.zeros(1, dtype=torch.int32, device=torch.device("cuda", idx))
-    return c
-
-
 def node_noise_bad_ids(device=None, reset: bool = False) -> int:
     """How many rows ``add_node_noise``'s forward met on ``device`` with an id
     outside the table (those rows pass ``x`` through and train nothing).
     Debugging only: reading the device counter synchronises."""
-    dev = torch.device("cuda" if device is None else device)
-    c = _bad_id_counter(dev)
-    n = int(c.item())
-    if reset:
-        c.zero_()
-    return n
-
-
-def _row_major(t: torch.Tensor) -> torch.Tensor:
-    """t addressable as rows of stride(0) elements (a row-sliced or
-    column-sliced view passes as it is, through its leading dimension)."""
-    if t.stride(1) != 1 or (t.size(0) > 1 and t.stride(0) < t.size(1)):
-        return t.contiguous()
-    return t
-
-
-def _ld(t: torch.Tensor) -> int:
-    return max(t.stride(0), t.size(1)) if t.size(0) > 1 else t.size(1)
+    return read_counter("bad-id", device, "add_node_noise", reset)
 
 
 class _AddNodeNoise(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, noise, n_id, rate: float, sign: bool):
-        xs, tab = _row_major(x), _row_major(noise)
+        (xs, ldx), (tab, ldt) = rows_ld(x), rows_ld(noise)
         n_rows, F = xs.shape
         out = torch.empty(n_rows, F, dtype=xs.dtype, device=xs.device)
         flags = _lib.NOISE_SIGN if sign else 0
-        bad = _bad_id_counter(xs.device)
+        bad = device_counter("bad-id", xs.device, "add_node_noise")
         # algorithmic bytes: x rows + table rows + out rows (+ the ids)
         nbytes = 3 * n_rows * F * 4 + (0 if n_id is None else n_rows * 8)
         with _timing.span("node_noise_fwd", nbytes):
             rc = _lib.load().ngnn_node_noise_fwd(
-                _lib.ptr(xs), _ld(xs), _lib.ptr(tab), _ld(tab), tab.size(0), _lib.ptr(n_id), n_rows, F,
+                _lib.ptr(xs), ldx, _lib.ptr(tab), ldt, tab.size(0), _lib.ptr(n_id), n_rows, F,
                 rate, flags, _lib.ptr(out), F, _lib.ptr(bad), _lib.stream_handle(xs.device))
         _lib.check(rc, "ngnn_node_noise_fwd")
-        ctx.rate, ctx.flags = rate, flags
+        ctx.rate, ctx.flags, ctx.ld = rate, flags, (ldx, ldt)
         ctx.save_for_backward(xs if sign else None, tab, n_id)
         return out
 
@@ -170,7 +140,7 @@ class _AddNodeNoise(torch.autograd.Function):
         dx = g if ctx.needs_input_grad[0] else None  # d out / d x = 1: the same tensor, no copy
         if not ctx.needs_input_grad[1]:
             return dx, None, None, None, None
-        gs = _row_major(g)
+        gs, ldg = rows_ld(g)
         n_rows, F = gs.shape
         n_nodes = tab.size(0)
         # no id list: row i is table row i -- stored, nothing to zero or to add up
@@ -183,8 +153,8 @@ class _AddNodeNoise(torch.autograd.Function):
         nbytes = 3 * n_rows * F * 4 + (0 if n_id is None else n_rows * 8)
         with _timing.span("node_noise_bwd", nbytes):
             rc = _lib.load().ngnn_node_noise_bwd(
-                _lib.ptr(gs), _ld(gs), _lib.ptr(xs), _ld(xs) if xs is not None else F, _lib.ptr(tab),
-                _ld(tab), n_nodes, _lib.ptr(n_id), int(scatter), n_rows, F, ctx.rate, ctx.flags,
+                _lib.ptr(gs), ldg, _lib.ptr(xs), ctx.ld[0] if xs is not None else F, _lib.ptr(tab),
+                ctx.ld[1], n_nodes, _lib.ptr(n_id), int(scatter), n_rows, F, ctx.rate, ctx.flags,
                 _lib.ptr(dst), F, None, _lib.stream_handle(gs.device))
         _lib.check(rc, "ngnn_node_noise_bwd")
         if n_id is None:
@@ -238,26 +208,11 @@ def add_node_noise(x: torch.Tensor, noise: torch.Tensor, n_id: torch.Tensor | No
 
 # ---- similarity top-k edge rewiring (ngnn_topk_rewire) ----
 
-_bad_endpoint_counters: dict = {}  # device index -> int32[1] on that device
-
-
-def _bad_endpoint_counter(device: torch.device) -> torch.Tensor:
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    c = _bad_endpoint_counters.get(idx)
-    if c is None:
-        c = _bad_endpoint_counters[idx] = torch.zeros(1, dtype=torch.int32, device=torch.device("cuda", idx))
-    return c
-
-
 def rewire_bad_endpoints(device=None, reset: bool = False) -> int:
     """How many edges ``topk_rewire`` met on ``device`` with an endpoint
     outside ``[0, N)`` (they are ignored).  Debugging only: reading the device
     counter synchronises."""
-    c = _bad_endpoint_counter(torch.device("cuda" if device is None else device))
-    n = int(c.item())
-    if reset:
-        c.zero_()
-    return n
+    return read_counter("bad-endpoint", device, "topk_rewire", reset)
 
 
 def topk_rewire(h: torch.Tensor, edge_index: torch.Tensor, device=None, k_percent: float = 0.1,
@@ -297,7 +252,7 @@ def topk_rewire(h: torch.Tensor, edge_index: torch.Tensor, device=None, k_percen
             or edge_index.dtype != torch.int64:
         raise ValueError("topk_rewire: edge_index must be an int64 tensor of shape [2, E]")
     dev = h.device
-    hs = _row_major(h.detach())
+    hs, ldh = rows_ld(h.detach())
     ei = edge_index.to(dev).contiguous()
     N, F = hs.shape
     E = ei.size(1)
@@ -320,11 +275,11 @@ def topk_rewire(h: torch.Tensor, edge_index: torch.Tensor, device=None, k_percen
         if return_selections:
             sel = torch.empty(4, k2, dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
-        bad = _bad_endpoint_counter(dev) if ws_bytes else None
+        bad = device_counter("bad-endpoint", dev, "topk_rewire") if ws_bytes else None
         # algorithmic bytes: h once, the edges, the outputs (the similarity tiles stay on chip)
         with _timing.span("topk_rewire", N * F * 4 + E * 16 + 2 * cap * 16):
             rc = lib.ngnn_topk_rewire(
-                _lib.ptr(hs), _ld(hs), N, F, _lib.ptr(ei[0]) if E else None, _lib.ptr(ei[1]) if E else None,
+                _lib.ptr(hs), ldh, N, F, _lib.ptr(ei[0]) if E else None, _lib.ptr(ei[1]) if E else None,
                 E, k2, _lib.ptr(pos), cap, _lib.ptr(neg), cap, _lib.ptr(counts), _lib.ptr(bad),
                 _lib.ptr(sel), _lib.ptr(ws), ws_bytes, _lib.stream_handle(dev))
     _lib.check(rc, "ngnn_topk_rewire")
@@ -361,7 +316,7 @@ def shuffle_pos(features: torch.Tensor, device=None, prob: float = 0.1, seed: in
         raise ValueError(f"shuffle_pos: features must be 2-D [N, F], got shape {tuple(features.shape)}")
     if features.dtype != torch.float32:
         raise TypeError(f"shuffle_pos: only float32 features are supported, got {features.dtype}")
-    x = _row_major(features.detach())
+    x, ldx = rows_ld(features.detach())
     N, F = x.shape
     m = int(F * prob)  # augmentation.py:94, same float arithmetic
     if not 0 <= m <= F:
@@ -370,7 +325,7 @@ def shuffle_pos(features: torch.Tensor, device=None, prob: float = 0.1, seed: in
         seed = int(torch.randint(0, 1 << 62, (1,)).item())
     out = torch.empty(N, F, dtype=torch.float32, device=x.device)
     with _timing.span("shuffle_pos", 2 * N * F * 4):
-        rc = _lib.load().ngnn_shuffle_rows(_lib.ptr(x), _ld(x), N, F, m, int(seed) & 0xFFFFFFFFFFFFFFFF,
+        rc = _lib.load().ngnn_shuffle_rows(_lib.ptr(x), ldx, N, F, m, int(seed) & 0xFFFFFFFFFFFFFFFF,
                                            _lib.ptr(out), F, _lib.stream_handle(x.device))
     _lib.check(rc, "ngnn_shuffle_rows")
     return out

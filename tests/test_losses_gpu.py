@@ -195,3 +195,86 @@ def test_bf16_logits_seed_rows_only():
     assert torch.equal(x.grad[B:], torch.zeros_like(x.grad[B:]))
     # (fp32 gradients equal to ~1 ulp, then each rounded to bf16: <= 1 bf16 ulp apart)
     torch.testing.assert_close(x.grad.float(), x2.grad.to(torch.bfloat16).float(), rtol=8e-3, atol=1e-7)
+
+
+# ---- two nodes of one backward pass never share a gradient buffer
+
+def _flip_matrix(C, p):
+    return (1 - p) * np.eye(C) + p / (C - 1) * (1 - np.eye(C))
+
+
+def test_ct_loss_twice_on_the_same_logits_adds_both_gradients():
+    """CTLoss(..., batch_size=B) twice on one [N, C] logits pair, different
+    labels: (l1a + l1b).backward() gives each model's logits the sum of the
+    two gradients taken separately (both nodes' zero-row buffers meet in one
+    backward pass), rows >= B exactly zero."""
+    N, B, C = 40, 33, 7
+    g = torch.Generator().manual_seed(11)
+    a = (torch.randn(N, C, generator=g) * 2).to(DEV).requires_grad_(True)
+    b = (torch.randn(N, C, generator=g) * 2).to(DEV).requires_grad_(True)
+    labels = [torch.randint(0, C, (N,), generator=g).to(DEV) for _ in range(2)]
+    ct = CTLoss(DEV)
+
+    def grads(label_sets):
+        outs = [ct(a, b, yl, 0.25, None, None, batch_size=B) for yl in label_sets]
+        a.grad = b.grad = None
+        sum(o[0] for o in outs).backward()
+        sum(o[1] for o in outs).backward()
+        return a.grad.clone(), b.grad.clone()
+
+    (a0, b0), (a1, b1) = grads(labels[:1]), grads(labels[1:])
+    assert float(a0.abs().max()) > 0 and float((a0 - a1).abs().max()) > 0  # (two different, nonzero gradients)
+    both_a, both_b = grads(labels)
+    torch.testing.assert_close(both_a, a0 + a1, rtol=1e-5, atol=1e-7)
+    torch.testing.assert_close(both_b, b0 + b1, rtol=1e-5, atol=1e-7)
+    assert torch.count_nonzero(both_a[B:]) == 0 and torch.count_nonzero(both_b[B:]) == 0
+
+
+def test_seed_xent_second_backward_next_to_a_pending_node():
+    """A node back-propagated again (retain_graph, a non-unit gradient) writes
+    into a buffer of its own, not one that another pending node of the same
+    (C, B) holds or could be handed."""
+    from ngnn.losses import seed_cross_entropy
+    N, B, C = 40, 33, 7
+    g = torch.Generator().manual_seed(12)
+    xs = [(torch.randn(N, C, generator=g) * 2).to(DEV).requires_grad_(True) for _ in range(2)]
+    y = torch.randint(0, C, (N,), generator=g).to(DEV)
+    l1, l2 = (seed_cross_entropy(x, y, B) for x in xs)  # two pending nodes
+    scale = torch.tensor(0.5, device=DEV)
+    first = torch.autograd.grad(l1, xs[0], scale, retain_graph=True)[0].clone()
+    again = torch.autograd.grad(l1, xs[0], scale, retain_graph=True)[0]
+    other = torch.autograd.grad(l2, xs[1], scale)[0]
+    assert again.data_ptr() != other.data_ptr()
+    for x, got in ((xs[0], first), (xs[0], again), (xs[1], other)):
+        x2 = x.detach().clone().requires_grad_(True)
+        ref = torch.autograd.grad(F.cross_entropy(x2[:B], y[:B]), x2, scale.clone())[0]
+        torch.testing.assert_close(got, ref, rtol=1e-5, atol=1e-7)
+        assert torch.count_nonzero(got[B:]) == 0
+
+
+@pytest.mark.parametrize("which", ["seed_cross_entropy", "backward_correction"])
+def test_bf16_loss_twice_on_the_same_logits_adds_both_gradients(which):
+    """As the CTLoss case, for the bf16 wrappers' bf16 zero-row buffers."""
+    from ngnn.losses import backward_correction, seed_cross_entropy
+    N, B, C = 40, 33, 7
+    g = torch.Generator().manual_seed(13)
+    x = (torch.randn(N, C, generator=g) * 2).to(DEV).to(torch.bfloat16).requires_grad_(True)
+    labels = [torch.randint(0, C, (N,), generator=g).to(DEV) for _ in range(2)]
+    mat = _flip_matrix(C, 0.3)
+
+    def loss(yl):
+        if which == "seed_cross_entropy":
+            return seed_cross_entropy(x, yl, B)
+        return backward_correction(x, yl, mat, C, batch_size=B)
+
+    def grad(label_sets):
+        x.grad = None
+        sum(loss(yl) for yl in label_sets).backward()
+        return x.grad.clone()
+
+    g0, g1 = grad(labels[:1]), grad(labels[1:])
+    assert g0.dtype == torch.bfloat16 and float((g0.float() - g1.float()).abs().max()) > 0
+    both = grad(labels)
+    # (the same two bf16 tensors added by autograd and here: the file's bf16 bar is generous)
+    torch.testing.assert_close(both.float(), (g0 + g1).float(), rtol=8e-3, atol=1e-7)
+    assert torch.equal(both[B:], torch.zeros_like(both[B:]))
