@@ -308,6 +308,13 @@ int ngnn_ct_loss_bwd(int model, const float *y, int64_t ld, int64_t B, int64_t C
  * ngnn_seg_agg_fwd, bit-identical); act = optional ReLU then optional
  * dropout with keep probability 1-p_drop and scale 1/(1-p_drop), drawn from a
  * counter-based hash of (seed, r, c) (no mask tensor; backward uses out > 0).
+ * A dropped element is +0.0 whatever its pre-activation (NaN and inf too);
+ * p_drop = 1 gives all +0.0.  Non-finite pre-activations otherwise: without
+ * ReLU a kept NaN stays NaN; ReLU passes NaN like torch.relu (y < 0 ? 0 : y)
+ * in every form but one -- the row-tile kernel's p_drop = 0.5 form
+ * (ngnn_sage_fwd_raw; one keep bit per element) takes ReLU as an integer
+ * max with 0 on the doubled value, so there a kept NaN with the sign bit set
+ * becomes +0.0 and only a positive-signed NaN passes.
  * W_l / W_r are the PyG Linear weights [Fo, K] packed by ngnn_pack_weight;
  * wl_packed may be NULL (no neighbour term; rowptr/col may then be NULL).
  * bias may be NULL.  x, out fp32 (outputs wider than 512 columns run as
@@ -380,6 +387,20 @@ size_t ngnn_sage_fwd_raw_workspace_bytes(int64_t K, int64_t Fo, int64_t n_rows);
 /* 1 when ngnn_sage_fwd_raw runs a [K -> Fo] layer on the wide path (exact:
  * the NGNN_MATH_EXACT_F32 mode), else 0. */
 int ngnn_sage_wide_preferred(int64_t K, int64_t Fo, int exact);
+/* The output columns per launch ("column slice") of the row-tile kernel for a
+ * [K -> Fo] ngnn_sage_fwd_raw call with a root term, or 0 when the call
+ * leaves that kernel (the wide path is preferred, K % 4 != 0, no slice fits
+ * the LDS, or the flags exclude it).  flags: the call's `reduce` argument --
+ * NGNN_REDUCE_* with NGNN_MATH_EXACT_F32 / NGNN_W_BF16 / NGNN_X_BF16 /
+ * NGNN_OUT_BF16 / NGNN_FWD_NARROW OR-ed in (NGNN_FWD_NARROW: the answer for a
+ * call that meets narrow mode's other conditions, then Fo itself).  A layer
+ * runs as ceil(Fo / slice) launches, slice s with its first column at
+ * s * slice; a slice is a multiple of 16 columns, so (slice >> 4) odd means
+ * every second launch starts mid-way through a 32-column dropout hash word.
+ * A pure function of its arguments (no device call; the same envelope code
+ * the forward runs).  A bad reduce or a non-positive size: NGNN_E_ARG; K or
+ * Fo >= 2^31: NGNN_E_RANGE.  Added within ABI 22. */
+int64_t ngnn_sage_fwd_slice_cols(int64_t K, int64_t Fo, int flags);
 int ngnn_sage_fwd_raw(const float *x, const float *const *x_dev, const int64_t *xrow,
                       const int64_t *const *xrow_dev, int64_t x_rows, int64_t ldx, int64_t K,
                       int64_t n_rows, const int32_t *n_rows_dev, int64_t n_edge_rows,

@@ -789,6 +789,26 @@ extern "C" size_t ngnn_sage_fwd_raw_workspace_bytes(int64_t K, int64_t Fo, int64
     return std::max({ngnn_pack_weight_bytes(Fo, K) + wl_b16_bytes(Fo, K), z, wide}) + kImgWsBytes;
 }
 
+// The routing of ngnn_sage_fwd_raw below, without a call: its order (narrow
+// mode, the wide path, the row-tile kernel) over the same rt_plan /
+// sage_wide_preferred, for raw weights with a root term.
+extern "C" int64_t ngnn_sage_fwd_slice_cols(int64_t K, int64_t Fo, int flags) {
+    const bool exact = (flags & NGNN_MATH_EXACT_F32) != 0, narrow = (flags & NGNN_FWD_NARROW) != 0;
+    const bool x_bf16 = (flags & NGNN_X_BF16) != 0, w_bf16 = (flags & NGNN_W_BF16) != 0;
+    const bool out_bf16 = (flags & NGNN_OUT_BF16) != 0;
+    const int reduce = flags & ~(NGNN_MATH_EXACT_F32 | NGNN_FWD_NARROW | NGNN_X_BF16 | NGNN_W_BF16 |
+                                 NGNN_WL_PREPACKED | NGNN_OUT_BF16);
+    NGNN_RETURN_IF(reduce < NGNN_REDUCE_SUM || reduce > NGNN_REDUCE_MAX || K <= 0 || Fo <= 0, NGNN_E_ARG);
+    NGNN_RETURN_IF(!fits_i32(K) || !fits_i32(Fo), NGNN_E_RANGE);
+    if ((x_bf16 && exact) || (out_bf16 && narrow) || K % 4 != 0) return 0;
+    RtPlan p;
+    if (narrow && reduce != NGNN_REDUCE_MAX && rt_plan(K, Fo, true, exact, w_bf16, reduce, true, false, p) && p.x3)
+        return p.slice;
+    if (!x_bf16 && !out_bf16 && sage_wide_preferred(K, Fo, exact)) return 0;
+    if (!rt_plan(K, Fo, true, exact, w_bf16, reduce, false, false, p) || (x_bf16 && !p.x3)) return 0;
+    return p.slice;
+}
+
 extern "C" int ngnn_sage_fwd_raw(const float *x, const float *const *x_dev, const int64_t *xrow,
                                  const int64_t *const *xrow_dev, int64_t x_rows, int64_t ldx,
                                  int64_t K, int64_t n_rows, const int32_t *n_rows_dev,

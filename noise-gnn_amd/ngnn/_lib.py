@@ -79,6 +79,7 @@ SIGNATURES = {
                              ctypes.c_float, _p]),
     "ngnn_sage_fwd_raw_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "ngnn_sage_wide_preferred": (_int, [_i64, _i64, _int]),
+    "ngnn_sage_fwd_slice_cols": (_i64, [_i64, _i64, _int]),  # (added within ABI 22)
     "ngnn_sage_fwd_raw": (_int, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _i64, _p, _p, _p, _p, _int, _p, _p,
                                  _i64, _p, _i64,
                                  _p, _i64, _int, ctypes.c_float, ctypes.c_uint64, _p, _p, _i64, _p,

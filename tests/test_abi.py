@@ -122,6 +122,15 @@ def test_argument_errors_return_before_launch():
     assert lib.ngnn_cast_tensors_ex(0, None, None, None, None, None, 2.0, None) == 0
     # zero-size work is a no-op success
     assert lib.ngnn_seg_agg_fwd(None, 4, 4, 1, None, 0, 1, 0, None, 4, None) == 0
+    # the forward's column-slice query: a pure function, bad sizes / reduce refused
+    assert lib.ngnn_sage_fwd_slice_cols(0, 64, 1) == -1
+    assert lib.ngnn_sage_fwd_slice_cols(64, 0, 1) == -1
+    assert lib.ngnn_sage_fwd_slice_cols(64, 64, 3) == -1
+    assert lib.ngnn_sage_fwd_slice_cols(64, 64, 1 | 0x4000) == -1
+    assert lib.ngnn_sage_fwd_slice_cols(2**31, 64, 1) == -5
+    assert lib.ngnn_sage_fwd_slice_cols(64, 2**31, 1) == -5
+    assert lib.ngnn_sage_fwd_slice_cols(64, 64, 1) == 256
+    assert lib.ngnn_sage_fwd_slice_cols(63, 64, 1) == 0
 
 
 def test_check_raises_with_message():
