@@ -1274,6 +1274,62 @@ int ngnn_split_accuracy(const void *logits, int64_t ld, int dtype, int64_t N, in
                         int64_t ignore_index, const int64_t *rows, int64_t M, int S, const int64_t *bounds,
                         int64_t *counts, int64_t *pred, int64_t *confusion, void *stream);
 
+/* ------------------------- symmetric-normalised GCN: the weighted aggregate
+ * Added within ABI 22 (new entries only: nothing existing changed, so the
+ * version did not move).
+ *
+ * PyG 2.5.1 GCNConv(normalize=True) [ext] for a Tensor edge_index, flow
+ * source -> target: out = D^-1/2 (A + I) D^-1/2 (x W^T) + b, with gcn_norm's
+ * self-loop rewrite (add_remaining_self_loops) and optional edge weights.
+ *
+ * ngnn_gcn_norm: one pass over the rows of a target-grouped CSR (rowptr
+ * int32 [n_rows + 1], col int32 [nnz]; w: fp32 [nnz] in CSR order or NULL =
+ * all ones), one thread per row, no atomics: deterministic.
+ *   add_self_loops != 0: every entry col == row leaves the degree; the row
+ *     gets one loop of weight loop_w[row] = 1, or, weighted, the weight of the
+ *     row's self-loop entry when it has one.  Several weighted self-loops on
+ *     one node are unspecified in PyG (an index_put with duplicates); here the
+ *     LAST in CSR (= edge) order wins.  deg = sum of the remaining entries'
+ *     weights in CSR order, the loop's weight added last, accumulated in
+ *     fp64 (a hub row's thousands of weights would cost dinv ulps in fp32).
+ *   add_self_loops == 0: deg = sum of every entry's weight in CSR order;
+ *     loop_w is not written (may be NULL).
+ *   dinv[row] = 1 / sqrt(deg): IEEE fp64 sqrt and divide, rounded once to
+ *     fp32 (no approximate reciprocal square root); deg == 0 gives 0 (PyG's
+ *     masked_fill(inf, 0)), a negative degree NaN, as PyG.
+ * Before any launch: n_rows < 0, a NULL rowptr or dinv, a NULL loop_w with
+ * add_self_loops (n_rows > 0): NGNN_E_ARG; n_rows >= 2^31: NGNN_E_RANGE.
+ * col (and w) may be NULL for a CSR without entries.
+ *
+ * ngnn_gcn_wagg: the weighted neighbour aggregate, for every row r < n_rows
+ *   out[r, :F] = bias + dinv[r] * ( sum over the row's entries e, CSR order,
+ *                  skipping col[e] == r when loop_w != NULL, of
+ *                  (w[e] * dinv[col[e]]) * z[col[e], :F]
+ *                  + (loop_w[r] * dinv[r]) * z[r, :F] )
+ * w, dinv, loop_w, bias: each nullable.  NULL w: ones; NULL dinv: ones; NULL
+ * loop_w: no loop term, and self-loop entries are ordinary entries; NULL
+ * bias: zeros.  z: [n_src, ldz] fp32 with col < n_src; with loop_w the row
+ * itself is read, so n_src >= n_rows.  fp32 accumulation in that fixed order,
+ * the loop term last, every product entering by a fused multiply-add and the
+ * additions compensated (Kahan: a row of a thousand equal terms would
+ * otherwise miss the fp32 bar by itself): bitwise reproducible.  One group of 4..64 lanes
+ * (the power of two at or above F / vector width) owns a row, a hub row
+ * included (its order stays fixed; its time is its degree's); the lanes load
+ * col, w and dinv[col] together and broadcast them; four gathered rows are in
+ * flight per lane; 16-B loads when F, ldz, ldo and the bases allow, 8-B or
+ * 4-B otherwise.  Plain vector stores, no atomics.  Row offsets are 64-bit.
+ * The coefficient of an edge is symmetric in its ends, so the input gradient
+ * is the same call on the source-grouped CSR with w permuted to that order
+ * and no bias.
+ * Before any launch: n_rows or F < 0, a NULL rowptr, a NULL z or out with
+ * n_rows > 0 and F > 0: NGNN_E_ARG; ldz or ldo < F: NGNN_E_SHAPE; n_rows or
+ * F >= 2^31: NGNN_E_RANGE. */
+int ngnn_gcn_norm(const int32_t *rowptr, const int32_t *col, const float *w, int64_t n_rows,
+                  int add_self_loops, float *dinv, float *loop_w, void *stream);
+int ngnn_gcn_wagg(const float *z, int64_t ldz, int64_t F, const int32_t *rowptr, const int32_t *col,
+                  const float *w, const float *dinv, const float *loop_w, const float *bias,
+                  int64_t n_rows, float *out, int64_t ldo, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

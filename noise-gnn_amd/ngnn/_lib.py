@@ -158,6 +158,9 @@ SIGNATURES = {
     "ngnn_confusion_max_classes": (_int, []),
     "ngnn_step_metrics": (_int, [_p, _i64, _int, _i64, _i64, _p, _i64, _p, _p, _p, _p, _p, _p]),
     "ngnn_split_accuracy": (_int, [_p, _i64, _int, _i64, _i64, _p, _i64, _p, _i64, _int, _p, _p, _p, _p, _p]),
+    # (added within ABI 22: symmetric-normalised GCN, the weighted aggregate)
+    "ngnn_gcn_norm": (_int, [_p, _p, _p, _i64, _int, _p, _p, _p]),
+    "ngnn_gcn_wagg": (_int, [_p, _i64, _i64, _p, _p, _p, _p, _p, _p, _i64, _p, _i64, _p]),
 }
 
 _lib = None

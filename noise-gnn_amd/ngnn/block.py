@@ -38,30 +38,39 @@ def _require_device_index(edge_index: torch.Tensor) -> None:
 
 
 class CSR:
-    __slots__ = ("rowptr", "col", "n_rows", "nnz")
+    __slots__ = ("rowptr", "col", "n_rows", "nnz", "eid")
 
-    def __init__(self, rowptr: torch.Tensor, col: torch.Tensor, n_rows: int):
+    def __init__(self, rowptr: torch.Tensor, col: torch.Tensor, n_rows: int,
+                 eid: torch.Tensor | None = None):
         self.rowptr, self.col, self.n_rows, self.nnz = rowptr, col, n_rows, col.numel()
+        self.eid = eid  # int32 [E]: entry -> position in edge_index, when asked for
 
     def degree(self) -> torch.Tensor:
         return (self.rowptr[1:] - self.rowptr[:-1])
 
 
-def build_csr(keys: torch.Tensor, vals: torch.Tensor, n_rows: int, keys_sorted: bool) -> CSR:
+def build_csr(keys: torch.Tensor, vals: torch.Tensor, n_rows: int, keys_sorted: bool,
+              want_eid: bool = False) -> CSR:
+    """want_eid: also keep ngnn_csr_build's entry -> edge permutation (the
+    order a per-edge array, such as GCNConv's edge_weight, is read in).  The
+    grouping is stable, so sorted keys have the identity: no array then."""
     lib = _lib.load()
     dev = keys.device
     E = keys.numel()
     rowptr = torch.empty(n_rows + 1, dtype=torch.int32, device=dev)
     col = torch.empty(max(E, 0), dtype=torch.int32, device=dev)
+    eid = None
+    if want_eid and not keys_sorted and E > 0:
+        eid = torch.empty(E, dtype=torch.int32, device=dev)
     ws, ws_bytes = None, 0
     if not keys_sorted and E > 0:
         ws_bytes = lib.ngnn_csr_workspace_bytes(E, n_rows)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     rc = lib.ngnn_csr_build(_lib.ptr(keys), _lib.ptr(vals), E, n_rows, int(keys_sorted),
-                            _lib.ptr(rowptr), _lib.ptr(col), None, _lib.ptr(ws), ws_bytes,
-                            _lib.stream_handle(dev))
+                            _lib.ptr(rowptr), _lib.ptr(col), _lib.ptr(eid) or None, _lib.ptr(ws),
+                            ws_bytes, _lib.stream_handle(dev))
     _lib.check(rc, "ngnn_csr_build")
-    return CSR(rowptr, col, n_rows)
+    return CSR(rowptr, col, n_rows, eid)
 
 
 class Block:
@@ -119,6 +128,12 @@ class Block:
         # the producer's loss head (ngnn.fused.LossHead: the step's
         # seed_cross_entropy taken by the two-layer forward), or None
         self.loss_head = None
+        # ngnn.ops.gcn_norm's records, keyed by (add_self_loops, edge_weight
+        # identity and version): the layers of a forward and its backward
+        # share one degree pass
+        self._gcn_norm = {}
+        self._eid = self._eid_t = False  # (False: not asked for yet)
+        self._n_rows_word = None  # device int32 [1] = n_dst, made by the first backward that needs it
 
     @property
     def rowptr(self):
@@ -134,6 +149,21 @@ class Block:
             ei = self.edge_index
             self._csr_t = build_csr(ei[0], ei[1], self.n_src, self.src_sorted)
         return self._csr_t
+
+    def edge_order(self, transposed: bool = False):
+        """int32 [E]: the position in ``edge_index`` of every entry of the
+        target-grouped CSR (``transposed``: of the source-grouped one), or
+        None when that is the identity (edges already sorted by that end).
+        Built lazily by one more ``ngnn_csr_build`` with its ``eid`` output
+        (the block's own CSR may come from a producer without one)."""
+        name = "_eid_t" if transposed else "_eid"
+        if getattr(self, name) is False:
+            ei = self.edge_index
+            k, v, n, srt = ((ei[0], ei[1], self.n_src, self.src_sorted) if transposed
+                            else (ei[1], ei[0], self.n_dst, self.dst_sorted))
+            setattr(self, name, None if (srt or self.E == 0)
+                    else build_csr(k, v, n, False, want_eid=True).eid)
+        return getattr(self, name)
 
 
 class _BlockCache:

@@ -1125,7 +1125,9 @@ class _ConvCall:
 
 
 def conv_supported(conv, x) -> bool:
+    # (a normalised GCNConv never runs as an un-normalised one-layer stack)
     return (x.is_cuda and x.dtype in _IO_DTYPES and x.dim() == 2
+            and not getattr(conv, "normalize", False)
             and all(p.dtype in _IO_DTYPES for p in conv.parameters()))
 
 
@@ -1145,6 +1147,105 @@ def gcn_conv(conv, x, block: Block) -> torch.Tensor:
     return _run_stack(_ConvCall, x, block, 0, None, [conv.lin.weight, conv.bias, None], "sum")
 
 
+def weighted_gcn_layers(model) -> list:
+    """Names of the model's GCNConv(normalize=True) layers: they run the
+    weighted aggregate (ngnn.ops.gcn_propagate) on their own per-conv path,
+    which none of the fused stacks, the block-free inference plan or a graph
+    slot (padded rows, a producer's CSR) knows about."""
+    from .nn import GCNConv
+    mods = model.named_modules() if isinstance(model, torch.nn.Module) else ()
+    return [name or type(m).__name__ for name, m in mods
+            if isinstance(m, GCNConv) and getattr(m, "normalize", False)]
+
+
+def _root_linear(x, block: Block, w, bias, span: str):
+    """out = x W^T (+ bias) on the row-tile kernel's root term alone (the
+    64-row kernel outside its envelope), as gcn_transform_first's z launch:
+    split-bf16 MFMA, exact-fp32 under set_exact_f32.  x: fp32 rows."""
+    N, K = x.shape
+    Fo = w.shape[0]
+    lib = _lib.load()
+    wd = w.detach() if w.stride(1) == 1 else w.detach().contiguous()
+    out = torch.empty(N, Fo, dtype=torch.float32, device=x.device)
+    if N == 0:
+        return out
+    ws = _workspace(x.device, "sage_fwd", lib.ngnn_sage_fwd_raw_workspace_bytes(K, Fo, N), zero=True)
+    root_rate = MFMA_F32_TFS * 1e12 * (1.0 if _exact_f32 else 16.0 / 6.0)
+    with _timing.span(span, (N * K + N * Fo) * 4, 2 * N * K * Fo, 2 * N * K * Fo / root_rate):
+        rc = _fwd_raw(x, rowptr=block.rowptr, col=block.col, reduce="sum", wr=wd, bias=bias, out=out,
+                      ws=ws)
+        if rc == _lib.E_SHAPE:
+            _gemm_layer(x, K, N, None, "sum", None, pack_weight(wd), bias, Fo, out, False, 0.0, 0)
+        else:
+            _lib.check(rc, "ngnn_sage_fwd_raw")
+    return out
+
+
+class _WeightedGCNConv(torch.autograd.Function):
+    """GCNConv on the weighted aggregate, aggregate-first: out = (A^ x) W^T +
+    b with A^ = D^-1/2 (A + I) D^-1/2 (or the plain weighted sum), for every
+    shape.  Backward: dW = dy^T (A^ x) and db = sum dy on ngnn_sage_wgrad (the
+    saved aggregate as its root operand), dx = A^^T (dy W): the root GEMM on
+    W^T, then the same aggregate kernel on the source-grouped CSR."""
+
+    @staticmethod
+    def forward(ctx, x, block: Block, norm, w, b):
+        from .ops import wagg_fwd
+        N, K = x.shape
+        agg = agg_buffer(N, K, x.device, w.shape[0])
+        wagg_fwd(x, block, norm, None, out=agg)
+        out = _root_linear(agg, block, w, b.detach() if b is not None else None, "gcn_norm_fwd")
+        ctx.block, ctx.norm = block, norm
+        ctx.save_for_backward(agg, w)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        from .ops import wagg_bwd
+        block, norm = ctx.block, ctx.norm
+        agg, w = ctx.saved_tensors
+        lib = _lib.load()
+        dev = dout.device
+        stream = _lib.stream_handle(dev)
+        N = block.n_dst
+        Fo, K = w.shape
+        dy = dout if (dout.stride(1) == 1 and dout.stride(0) >= Fo) else dout.contiguous()
+        dw = db = dx = None
+        if N == 0:
+            return (torch.zeros(0, K, device=dev), None, None, torch.zeros_like(w),
+                    torch.zeros(Fo, device=dev))
+        if ctx.needs_input_grad[3] or ctx.needs_input_grad[4]:
+            dw, db = torch.empty_like(w, memory_format=torch.contiguous_format), torch.empty(
+                Fo, dtype=torch.float32, device=dev)
+            # the kernel's neighbour-term gradient (dy^T agg with edgeless rows
+            # read as 0) is not this layer's: it lands in a scratch buffer
+            scratch = _workspace(dev, "gcn_dwr", w.numel() * 4).view(torch.float32)[:w.numel()].view(Fo, K)
+            ws = _workspace(dev, "wgrad", lib.ngnn_sage_wgrad_workspace_bytes(Fo, K))
+            # every row carries a gradient: the row bound is N, a device word
+            # kept on the block (one fill per mini-batch, shared by its layers;
+            # const_bounds' process-wide cache would keep one per block size)
+            bound = block._n_rows_word
+            if bound is None:
+                bound = block._n_rows_word = torch.full((1,), N, dtype=torch.int32, device=dev)
+            with _timing.span("gcn_norm_wgrad", 0, 0):
+                rc = lib.ngnn_sage_wgrad(
+                    _lib.ptr(dy), dy.stride(0), None, Fo, 1.0, _lib.ptr(agg), None, None, None, 0, 0,
+                    agg.stride(0), _lib.ptr(agg), agg.stride(0), _lib.ptr(block.rowptr), N,
+                    bound.data_ptr(), Fo, K, _lib.ptr(scratch), _lib.ptr(db), _lib.ptr(dw),
+                    _lib.ptr(ws), ws.numel(), stream)
+            _lib.check(rc, "ngnn_sage_wgrad")
+        if ctx.needs_input_grad[0]:
+            dagg = _root_linear(dy, block, w.detach().t().contiguous(), None, "gcn_norm_dgrad")
+            dx = wagg_bwd(dagg, block, norm)
+        return dx, None, None, dw, db
+
+
+def gcn_weighted_conv(conv, x, block: Block, norm) -> torch.Tensor:
+    """GCNConv(normalize=True) / GCNConv with an edge_weight: fp32 only."""
+    return _WeightedGCNConv.apply(x, block, norm, conv.lin.weight, conv.bias)
+
+
 def zero_copy_ok(model, n_rows: int, in_dim: int, table_rows: int = 0) -> bool:
     """Can a HIP-graph slot hand this model's layer 0 the batch's feature rows
     in place (ngnn_sage_fwd_raw's x_dev)?  Only the fused SAGE stack reads
@@ -1160,6 +1261,8 @@ def zero_copy_ok(model, n_rows: int, in_dim: int, table_rows: int = 0) -> bool:
     if not isinstance(getattr(model, "convs", None), torch.nn.ModuleList):
         return False
     if getattr(model, "use_bn", False):
+        return False
+    if weighted_gcn_layers(model):  # (per-conv path: reads the slot's rows, not x_dev)
         return False
     c0 = model.convs[0]
     wide = False
@@ -1189,7 +1292,9 @@ def zero_copy_ok(model, n_rows: int, in_dim: int, table_rows: int = 0) -> bool:
 
 
 def gcn_stack_supported(model, x) -> bool:
+    # (normalised layers take the per-conv path: the stack sums raw rows)
     return (x.is_cuda and x.dtype in _IO_DTYPES and x.dim() == 2
+            and not any(getattr(c, "normalize", False) for c in model.convs)
             and all(p.dtype in _IO_DTYPES for p in model.parameters()))
 
 

@@ -42,6 +42,7 @@ from .losses import seed_cross_entropy
 class GraphedTrainStep:
     def __init__(self, model, optimizer, batch_size: int, n_cap: int, e_cap: int, in_dim: int,
                  device, reducer=None, loss_fn=None, warmup: int = 3):
+        _refuse_weighted_gcn(model)
         if not optimizer.defaults.get("capturable", False):
             raise ValueError("GraphedTrainStep needs an optimizer built with capturable=True")
         self.model, self.opt, self.reducer = model, optimizer, reducer
@@ -390,13 +391,26 @@ def _lin_w(conv):
     return getattr(lin, "weight", None)
 
 
+def _refuse_weighted_gcn(model) -> None:
+    """A graph slot pads its rows and edges and builds its CSR in the slot
+    kernel; neither knows the normalised layer's coefficients."""
+    from .fused import weighted_gcn_layers
+    names = weighted_gcn_layers(model)
+    if names:
+        raise ValueError(f"a captured step cannot hold GCNConv(normalize=True) layers ({', '.join(names)}): "
+                         "train them eagerly (the slot's padded rows and its CSR producer know nothing "
+                         "of the normalisation coefficients)")
+
+
 def _prepack_target(model):
     """(W_l, packed buffer) of layer 0 when the model is a fused SAGE stack
     with fp32 weights (a bf16 model's weights are widened copies: no stable
     address), else None."""
-    from .fused import pack_weight
+    from .fused import pack_weight, weighted_gcn_layers
     from .models import SAGE
     if not isinstance(model, SAGE) or getattr(model, "use_bn", False):
+        return None
+    if weighted_gcn_layers(model):  # (none in a SAGE today: the slot's pack is for fused stacks only)
         return None
     w = model.convs[0].lin_l.weight
     if w.dtype != torch.float32 or not w.is_cuda or w.stride(1) != 1:
@@ -481,6 +495,7 @@ class GraphedCoTeachingStep(GraphedTrainStep):
 
     def __init__(self, model1, optimizer1, model2, optimizer2, criterion, batch_size: int, n_cap: int,
                  e_cap: int, in_dim: int, device, noise_or_not=None, warmup: int = 3):
+        _refuse_weighted_gcn(model2)
         super().__init__(model1, optimizer1, batch_size, n_cap, e_cap, in_dim, device, warmup=warmup)
         if not optimizer2.defaults.get("capturable", False):
             raise ValueError("GraphedCoTeachingStep needs optimizers built with capturable=True")

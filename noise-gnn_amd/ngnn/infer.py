@@ -72,6 +72,10 @@ def _layer_spec(conv, last: bool):
         aggr = "sum" if conv.aggr == "add" else conv.aggr
         return aggr, conv.lin_l.weight, conv.lin_r.weight, conv.lin_l.bias, not last
     if isinstance(conv, GCNConv):
+        if conv.normalize:
+            # the block-free plan draws the seed rows' in-edges only: it cannot
+            # know the sources' degrees on the sampled block -- the loop plan
+            return None
         return "sum", conv.lin.weight, None, conv.bias, not last
     return None
 

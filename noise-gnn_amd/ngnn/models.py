@@ -114,15 +114,19 @@ class SAGE(nn.Module):
 
 
 class SimpleGCN(nn.Module):
-    def __init__(self, in_size, hidden_size, out_size, num_layers, dropout=0.5, use_bn=False):
+    def __init__(self, in_size, hidden_size, out_size, num_layers, dropout=0.5, use_bn=False,
+                 normalize=False):
         super().__init__()
         self.num_layers = num_layers
         self.dropout = dropout
+        # normalize=True: every layer is the symmetric-normalised GCNConv (not
+        # the reference's choice, convolution.py:19-23; the per-conv path)
+        self.normalize = bool(normalize)
         self.convs = nn.ModuleList()
-        self.convs.append(GCNConv(in_size, hidden_size, normalize=False))
+        self.convs.append(GCNConv(in_size, hidden_size, normalize=normalize))
         for _ in range(num_layers - 2):
-            self.convs.append(GCNConv(hidden_size, hidden_size, normalize=False))
-        self.convs.append(GCNConv(hidden_size, out_size, normalize=False))
+            self.convs.append(GCNConv(hidden_size, hidden_size, normalize=normalize))
+        self.convs.append(GCNConv(hidden_size, out_size, normalize=normalize))
 
     def reset_parameters(self):
         for conv in self.convs:
@@ -270,7 +274,7 @@ class NGNN(object):
 
     def __init__(self, in_size=100, hidden_size=128, out_size=47, num_layers=2, dropout=0.5,
                  lr=0.001, optimizer='adam', module='sage', nbr_nodes=1, use_bn=False, wd=0.0005,
-                 aggr='mean'):
+                 aggr='mean', gcn_normalize=False):
         self.criterion = None
         self.score_func = None
         self.metric_name = None
@@ -281,6 +285,7 @@ class NGNN(object):
         self.module = module
         self.use_bn = use_bn
         self.aggr = aggr
+        self.gcn_normalize = gcn_normalize
         self.init_network()
         self.init_optimizer()
 
@@ -288,7 +293,7 @@ class NGNN(object):
         if self.module == 'gcn':
             self.network = SimpleGCN(in_size=self.in_size, hidden_size=self.hidden_size,
                                      out_size=self.out_size, num_layers=self.num_layers,
-                                     dropout=self.dropout)
+                                     dropout=self.dropout, normalize=self.gcn_normalize)
         elif self.module == 'sage':
             self.network = SAGE(in_size=self.in_size, hidden_size=self.hidden_size,
                                 out_size=self.out_size, num_layers=self.num_layers,

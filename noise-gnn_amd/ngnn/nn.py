@@ -1,4 +1,4 @@
-"""Drop-in conv layers: ``SAGEConv`` and ``GCNConv(normalize=False)``.
+"""Drop-in conv layers: ``SAGEConv`` and ``GCNConv``.
 
 Same constructor signatures, forward(x, edge_index), reset_parameters(),
 sub-module names and state-dict keys as PyG 2.5.1's classes the reference
@@ -8,6 +8,8 @@ imports (``sage.py:4``, ``convolution.py:4``):
   out = lin_l(aggr_{j->i} x_j) + lin_r(x_i)          (sage.py:16-19, :34)
 * GCNConv(normalize=False): ``lin.weight [out,in]`` (glorot), ``bias [out]`` (zeros)
   out = sum_{j->i} (x W^T)_j + bias                  (convolution.py:19-23, :31)
+* GCNConv(normalize=True): same parameters,
+  out = D^-1/2 (A + I) D^-1/2 x W^T + bias           (PyG gcn_norm [ext])
 
 ``forward`` also accepts a prebuilt :class:`ngnn.block.Block` in place of
 ``edge_index`` (the model wrappers build one per mini-batch).  On the GPU
@@ -107,13 +109,36 @@ class SAGEConv(nn.Module):
 
 
 class GCNConv(nn.Module):
+    """PyG 2.5.1 ``GCNConv`` [ext] for a Tensor ``edge_index``.
+
+    ``normalize=False`` (this class's default -- PyG's is ``True``; the
+    reference's ``SimpleGCN`` passes ``False`` and existing models rely on
+    it): ``out = sum_{j->i} (x W^T)_j + b`` on the fused kernels.
+    ``normalize=True``: the Kipf-Welling layer ``D^-1/2 (A + I) D^-1/2 x W^T +
+    b`` with ``gcn_norm``'s self-loop rewrite (``add_self_loops=None`` means
+    ``= normalize``), degrees counted on the edges passed in.  ``forward``
+    takes an optional ``edge_weight`` (fp32 ``[E]``, no gradient) in either
+    mode.  The normalised / weighted path is fp32 only and runs eagerly
+    (``ngnn.ops.gcn_norm`` + the weighted aggregate kernel, the linear part
+    on the hand-written GEMM kernels: no library GEMM)."""
+
     def __init__(self, in_channels: int, out_channels: int, normalize: bool = False,
-                 add_self_loops: bool | None = None, bias: bool = True, **kwargs):
+                 add_self_loops: bool | None = None, bias: bool = True, improved: bool = False,
+                 cached: bool = False, **kwargs):
         super().__init__()
-        if normalize or add_self_loops or not bias:
+        if add_self_loops is None:
+            add_self_loops = bool(normalize)
+        if (add_self_loops and not normalize) or not bias:
             raise NotImplementedError(
-                "the reference only uses GCNConv(in, out, normalize=False) (convolution.py:19-23)")
+                "GCNConv: add_self_loops needs normalize=True, and bias=False is not implemented "
+                "(the reference uses GCNConv(in, out, normalize=False), convolution.py:19-23)")
+        if normalize and improved:
+            raise NotImplementedError("GCNConv(normalize=True, improved=True) is not implemented")
+        if normalize and cached:
+            raise NotImplementedError("GCNConv(normalize=True, cached=True) is not implemented "
+                                      "(the norm record is cached per block instead)")
         self.in_channels, self.out_channels = in_channels, out_channels
+        self.normalize, self.add_self_loops = bool(normalize), bool(add_self_loops)
         self.lin = Linear(in_channels, out_channels, bias=False, weight_initializer="glorot")
         self.bias = nn.Parameter(torch.zeros(out_channels))
 
@@ -121,9 +146,17 @@ class GCNConv(nn.Module):
         self.lin.reset_parameters()
         self.bias.data.zero_()
 
-    def forward(self, x: torch.Tensor, edge_index) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, edge_index, edge_weight=None) -> torch.Tensor:
+        weighted = self.normalize or edge_weight is not None
+        if weighted:  # (refused before anything touches the device)
+            for name, t in (("x", x), ("lin.weight", self.lin.weight), ("bias", self.bias)):
+                if t.dtype != torch.float32:
+                    raise TypeError("GCNConv: the normalised / weighted path is float32 only, "
+                                    f"{name} is {t.dtype}")
         block = get_block(edge_index, x.size(0))
         from . import fused
+        if weighted:
+            return self._forward_weighted(x, block, edge_weight)
         if fused.conv_supported(self, x):
             # per-conv drop-in (convolution.py:29-35 with this class in place of
             # PyG's): one autograd node on the hand-written kernels
@@ -131,5 +164,18 @@ class GCNConv(nn.Module):
         h = self.lin(x)
         return segment_aggregate(h, block, "sum") + self.bias
 
+    def _forward_weighted(self, x, block, edge_weight):
+        from . import fused
+        from .ops import _gcn_record
+        if not x.is_cuda:
+            raise RuntimeError("ngnn runs on the GPU only: x is on the CPU")
+        if x.dim() != 2:
+            raise ValueError(f"x must be 2-D [N, F], got shape {tuple(x.shape)}")
+        if x.size(0) != block.n_src:
+            raise ValueError(f"x has {x.size(0)} rows but the block has {block.n_src} nodes")
+        norm = _gcn_record(block, edge_weight, self.add_self_loops, self.normalize)
+        return fused.gcn_weighted_conv(self, x, block, norm)
+
     def __repr__(self):
-        return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels})"
+        extra = ", normalize=True" if self.normalize else ""
+        return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels}{extra})"

@@ -13,6 +13,8 @@ counting as a tie when the maximum is 0).
 """
 from __future__ import annotations
 
+import weakref
+
 import torch
 
 from . import _lib, _timing
@@ -87,6 +89,179 @@ def segment_aggregate(x: torch.Tensor, block: Block, reduce: str = "mean") -> to
     if reduce not in _lib.REDUCE:
         raise ValueError(f"unsupported aggregation {reduce!r} (expected mean, sum/add or max)")
     return _SegmentAggregate.apply(x, block, reduce)
+
+
+# ---- symmetric-normalised GCN: gcn_norm and the weighted aggregate ----
+
+class GCNNorm:
+    """What ``gcn_norm`` returns: ``dinv`` / ``loop_w`` (fp32 ``[N]``; None
+    when the record normalises nothing / replaces no self-loops), ``w`` (the
+    edge weights in target-grouped CSR order, None = ones) and ``w_t()`` (the
+    same in source-grouped order, built at its first use: the backward's).
+    ``edge_weight`` is the caller's tensor, kept for the cache's identity
+    check alone; both orders are built from ``_ew``, its dense copy (the
+    kernels read ``E`` consecutive floats).  The block is held weakly: the
+    block's cache holds the record, and a strong reference back would keep
+    the device arrays until the cycle collector runs."""
+    __slots__ = ("_block", "add_self_loops", "normalize", "edge_weight", "_ew", "dinv", "loop_w", "w", "_w_t")
+
+    def __init__(self, block, add_self_loops, normalize, edge_weight, ew, dinv, loop_w, w):
+        self._block = weakref.ref(block)
+        self.add_self_loops, self.normalize = add_self_loops, normalize
+        self.edge_weight, self._ew, self.dinv, self.loop_w, self.w = edge_weight, ew, dinv, loop_w, w
+        self._w_t = False
+
+    @property
+    def block(self):
+        return self._block()
+
+    def w_t(self):
+        if self._w_t is False:
+            if self._ew is None:
+                self._w_t = None
+            else:
+                block = self.block
+                if block is None:
+                    raise RuntimeError("gcn_norm: the record's block is gone")
+                order = block.edge_order(transposed=True)
+                self._w_t = self._ew if order is None else self._ew.index_select(0, order)
+        return self._w_t
+
+
+def _check_edge_weight(edge_weight, block: Block) -> torch.Tensor:
+    if not isinstance(edge_weight, torch.Tensor):
+        raise TypeError("edge_weight must be a torch.Tensor")
+    if not edge_weight.is_cuda:
+        raise RuntimeError("ngnn runs on the GPU only: edge_weight is on the CPU")
+    if edge_weight.dtype != torch.float32:
+        raise TypeError(f"edge_weight: only float32 is supported, got {edge_weight.dtype}")
+    if edge_weight.dim() != 1 or edge_weight.numel() != block.E:
+        raise ValueError(f"edge_weight must be 1-D with one weight per edge ({block.E}), "
+                         f"got shape {tuple(edge_weight.shape)}")
+    if edge_weight.device != block.device:
+        raise ValueError(f"edge_weight on {edge_weight.device}, the block on {block.device}")
+    if edge_weight.requires_grad:
+        raise NotImplementedError("edge_weight.requires_grad: there is no gradient to the edge weights")
+    return edge_weight
+
+
+def _gcn_record(block: Block, edge_weight, add_self_loops: bool, normalize: bool) -> GCNNorm:
+    """The block's cached record for (add_self_loops, normalize, edge_weight
+    identity and version): one ``ngnn_gcn_norm`` launch per block and key."""
+    if block.n_src != block.n_dst:
+        raise ValueError("gcn_norm needs a square block (sources == targets)")
+    ew = None if edge_weight is None else _check_edge_weight(edge_weight, block)
+    key = (bool(add_self_loops), bool(normalize), None if ew is None else (id(ew), ew._version))
+    hit = block._gcn_norm.get(key)
+    if hit is not None and hit.edge_weight is ew:  # (the record holds ew: its id cannot be reused)
+        return hit
+    w = None
+    if ew is not None:
+        ew = ew.contiguous()  # (a column of edge_attr: the kernels read consecutive floats)
+        order = block.edge_order()
+        w = ew if order is None else ew.index_select(0, order)
+    dinv = loop_w = None
+    N = block.n_dst
+    if normalize:
+        dinv = torch.empty(N, dtype=torch.float32, device=block.device)
+        if add_self_loops:
+            loop_w = torch.empty(N, dtype=torch.float32, device=block.device)
+        with _timing.span("gcn_norm", block.E * (8 if w is not None else 4) + N * 16):
+            rc = _lib.load().ngnn_gcn_norm(_lib.ptr(block.rowptr), _lib.ptr(block.col), _lib.ptr(w), N,
+                                           int(bool(add_self_loops)), _lib.ptr(dinv), _lib.ptr(loop_w),
+                                           _lib.stream_handle(block.device))
+        _lib.check(rc, "ngnn_gcn_norm")
+    rec = GCNNorm(block, bool(add_self_loops), bool(normalize), edge_weight, ew, dinv, loop_w, w)
+    if len(block._gcn_norm) >= 4:
+        block._gcn_norm.clear()
+    block._gcn_norm[key] = rec
+    return rec
+
+
+def gcn_norm(block_or_edge_index, edge_weight=None, num_nodes=None, add_self_loops=True) -> GCNNorm:
+    """PyG 2.5.1's ``gcn_norm`` [ext] for a Tensor ``edge_index`` (flow source
+    -> target) as a record of per-node arrays instead of a rewritten edge
+    list: with ``add_self_loops`` every self-loop edge is dropped and every
+    node gets one loop (weight 1, or the weight of its existing self-loop
+    edge -- the last in edge order when it has several, where PyG is
+    unspecified); ``deg`` = the weights into each node, ``dinv = deg^-1/2``
+    (0 where ``deg == 0``).  An edge's coefficient is ``dinv[s] * w * dinv[t]``.
+    One launch (``ngnn_gcn_norm``), cached on the block: every layer of a
+    forward and the backward share it.  ``edge_weight``: fp32 ``[E]`` on the
+    block's device, no gradient.  ``num_nodes`` is needed with a raw
+    ``edge_index``."""
+    from .block import get_block
+    if isinstance(block_or_edge_index, Block):
+        block = block_or_edge_index
+    else:
+        if num_nodes is None:
+            raise ValueError("gcn_norm: pass num_nodes with a raw edge_index")
+        block = get_block(block_or_edge_index, int(num_nodes))
+    return _gcn_record(block, edge_weight, bool(add_self_loops), True)
+
+
+def _wagg(z, ldz, F, csr, w, norm: GCNNorm, bias, n_rows, out):
+    # algorithmic bytes: E (4F + 8 [+4 weighted]) + N (8F + 12)  (DESIGN.md 5n)
+    nbytes = csr.nnz * (4 * F + 8 + (4 if w is not None else 0)) + n_rows * (8 * F + 12)
+    with _timing.span("gcn_wagg", nbytes):
+        rc = _lib.load().ngnn_gcn_wagg(
+            _lib.ptr(z), ldz, F, _lib.ptr(csr.rowptr), _lib.ptr(csr.col), _lib.ptr(w),
+            _lib.ptr(norm.dinv), _lib.ptr(norm.loop_w), _lib.ptr(bias), n_rows, _lib.ptr(out),
+            out.stride(0) if out.size(0) > 1 else max(F, 1), _lib.stream_handle(z.device))
+    _lib.check(rc, "ngnn_gcn_wagg")
+    return out
+
+
+def wagg_fwd(z: torch.Tensor, block: Block, norm: GCNNorm, bias=None, out=None) -> torch.Tensor:
+    """``ngnn_gcn_wagg`` over the target-grouped CSR, no autograd."""
+    zs, ldz = rows_ld(z)
+    N, F = block.n_dst, zs.size(1)
+    if out is None:
+        out = torch.empty(N, F, dtype=torch.float32, device=zs.device)
+    return _wagg(zs, ldz, F, block.csr, norm.w, norm, bias, N, out)
+
+
+def wagg_bwd(g: torch.Tensor, block: Block, norm: GCNNorm) -> torch.Tensor:
+    """The input gradient of ``wagg_fwd``: the same entry on the
+    source-grouped CSR (an edge's coefficient is symmetric in its ends)."""
+    gs, ldg = rows_ld(g)
+    N, F = block.n_src, gs.size(1)
+    out = torch.empty(N, F, dtype=torch.float32, device=gs.device)
+    return _wagg(gs, ldg, F, block.transposed(), norm.w_t(), norm, None, N, out)
+
+
+class _GCNPropagate(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, block: Block, norm: GCNNorm, bias):
+        ctx.block, ctx.norm = block, norm
+        return wagg_fwd(z, block, norm, bias)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        dz = wagg_bwd(g, ctx.block, ctx.norm) if ctx.needs_input_grad[0] else None
+        db = g.sum(0) if ctx.needs_input_grad[3] else None
+        return dz, None, None, db
+
+
+def gcn_propagate(z: torch.Tensor, block: Block, norm: GCNNorm, bias=None) -> torch.Tensor:
+    """``out_i = bias + sum over edges e into i of dinv[s_e] w_e dinv[i]
+    z[s_e]`` (+ the node's loop term when ``norm`` replaced the self-loops):
+    PyG's ``GCNConv.propagate`` on ``gcn_norm``'s output, without the ``[E,
+    F]`` message tensor.  fp32, GPU only; ``z`` passes through its leading
+    dimension.  The forward and the gradient with respect to ``z`` (the same
+    kernel on ``block.transposed()``) sum in a fixed order: bitwise
+    reproducible.  The bias gradient is torch's column sum ``g.sum(0)``, not
+    one of this library's fixed-order sums (``GCNConv`` does not take it from
+    here: its ``db`` comes from ``ngnn_sage_wgrad``)."""
+    z = _check_features(z, "z")
+    if z.size(0) != block.n_src:
+        raise ValueError(f"z has {z.size(0)} rows but the block has {block.n_src} nodes")
+    if norm.block is not block:
+        raise ValueError("gcn_propagate: norm was computed for another block")
+    if bias is not None and (not bias.is_cuda or bias.dtype != torch.float32 or bias.numel() != z.size(1)):
+        raise TypeError("gcn_propagate: bias must be a float32 CUDA tensor with one value per column")
+    return _GCNPropagate.apply(z, block, norm, bias)
 
 
 def sample_seed_rows(graph, fanout: int, batch_size: int, seed0: int, seed_stride: int, r0: int,
