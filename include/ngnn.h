@@ -1330,6 +1330,72 @@ int ngnn_gcn_wagg(const float *z, int64_t ldz, int64_t F, const int32_t *rowptr,
                   const float *w, const float *dinv, const float *loop_w, const float *bias,
                   int64_t n_rows, float *out, int64_t ldo, void *stream);
 
+/* ------------------------------------------ fused ReLU-BatchNorm-dropout
+ * Added within ABI 22 (new entries only: nothing existing changed, so the
+ * version did not move).
+ *
+ * nn.BatchNorm1d over the n_rows nodes of x [n_rows, ldx] fp32 (columns: the
+ * F features), with the ReLU in front of it and the hash dropout behind it
+ * folded in: what SAGE / SAGEPL(use_bn=True) run per hidden layer
+ * (DESIGN.md section 5o).  a = relu(x) when relu != 0, else x; torch's relu: a
+ * NaN stays a NaN.
+ *
+ * ngnn_bn_fwd_train: out = drop(gamma * (a - mean) * invstd + beta), mean and
+ *   var the per-column batch mean and BIASED variance of a, invstd =
+ *   1 / sqrt(var + eps).  drop is ngnn_device.h::Dropout on
+ *   (seed ^ *seed_dev, row, column) (seed_dev nullable): keep threshold
+ *   ceil(p_drop * 256), survivors scaled by 256 / (256 - thresh), p_drop = 0.5
+ *   in bit form; a dropped element is +0.0, p_drop = 0 is no dropout, 1 drops
+ *   everything.  mean[F] and invstd[F] are saved for ngnn_bn_bwd, and with
+ *   them mean_lo[F] = the fp64 mean minus its fp32 rounding: the kernels
+ *   subtract the pair, (a - mean) - mean_lo, because fp32 alone holds a mean
+ *   of 4096 to 2.4e-4, which would be the error of that column's every
+ *   output (torch's CPU BatchNorm, the yardstick, normalises in fp64).  The running
+ *   statistics move on the device as nn.BatchNorm1d's: running_mean =
+ *   (1 - m) running_mean + m mean, running_var likewise with the UNBIASED
+ *   var n / (n - 1), *num_batches_tracked += 1; m = momentum, or, momentum < 0
+ *   (torch's None), 1 / num_batches_tracked after the increment.
+ *   Statistics: never E[a^2] - E[a]^2.  Every thread takes eight rows' mean
+ *   and squared deviations around it; chunks, lane groups, the slabs of
+ *   ngnn_bn_slab_rows() rows (one (mean, M2) partial per slab and column in
+ *   ws; counts follow from the indices) and the finalise kernel's slab lanes
+ *   are merged by Chan's formula in one fixed order in fp64, then rounded once
+ *   to fp32: no atomics, bitwise reproducible.  Three launches (partials,
+ *   finalise, apply); ws holds ngnn_bn_workspace_bytes(n_rows, F) bytes,
+ *   8-byte aligned.
+ * ngnn_bn_fwd_eval: out = gamma * (a - running_mean) / sqrt(running_var + eps)
+ *   + beta, one launch, nothing updated, no dropout.
+ * ngnn_bn_bwd: with g = dout * keep * scale (the keep mask regenerated from
+ *   the same seed pair) and xhat = (a - mean) * invstd:
+ *     dbeta = sum_r g, dgamma = sum_r g * xhat (fp64 sums in the forward's
+ *     fixed order, rounded once),
+ *     dx = [relu: x > 0] gamma invstd (g - dbeta / n - xhat dgamma / n).
+ *   dx == NULL skips the dx launch (an input that needs no gradient).  At
+ *   most three launches; the same workspace size.
+ * A NaN in a column makes that column's statistics, outputs, running
+ * statistics and gradients NaN and leaves every other column alone.
+ * 16-B accesses when F, every leading dimension and every base allow, 4-B
+ * otherwise; consecutive lanes take consecutive columns.
+ * Before any launch: n_rows < 2 (train, bwd: no batch statistics of one row),
+ * n_rows < 0 (eval), F <= 0, a NULL required pointer, p_drop outside [0, 1],
+ * eps < 0, momentum > 1: NGNN_E_ARG; a leading dimension < F: NGNN_E_SHAPE;
+ * n_rows > 2^31 - 257 or F > 2^20: NGNN_E_RANGE; ws NULL, misaligned or too
+ * small: NGNN_E_WORKSPACE.  ngnn_bn_fwd_eval with n_rows == 0: success. */
+int ngnn_bn_slab_rows(void);
+size_t ngnn_bn_workspace_bytes(int64_t n_rows, int64_t F);
+int ngnn_bn_fwd_train(const float *x, int64_t ldx, int64_t n_rows, int64_t F, int relu, const float *gamma,
+                      const float *beta, double eps, double momentum, float *running_mean, float *running_var,
+                      int64_t *num_batches_tracked, float p_drop, uint64_t seed, const uint64_t *seed_dev,
+                      float *out, int64_t ldo, float *mean, float *mean_lo, float *invstd, void *ws,
+                      size_t ws_bytes, void *stream);
+int ngnn_bn_fwd_eval(const float *x, int64_t ldx, int64_t n_rows, int64_t F, int relu, const float *gamma,
+                     const float *beta, double eps, const float *running_mean, const float *running_var,
+                     float *out, int64_t ldo, void *stream);
+int ngnn_bn_bwd(const float *dout, int64_t ldg, const float *x, int64_t ldx, int64_t n_rows, int64_t F, int relu,
+                const float *gamma, const float *mean, const float *mean_lo, const float *invstd, float p_drop,
+                uint64_t seed, const uint64_t *seed_dev, float *dgamma, float *dbeta, float *dx, int64_t ldd,
+                void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,8 +11,8 @@ from .metrics import EpochMeter, split_accuracy
 from .models import NGNN, SAGE, SAGEPL, SimpleGCN
 from .nn import GCNConv, Linear, SAGEConv
 from .noise import flip_label, noise_matrix
-from .ops import add_node_noise, segment_aggregate, shuffle_pos, topk_rewire
+from .ops import add_node_noise, batch_norm_act, segment_aggregate, shuffle_pos, topk_rewire
 
 __all__ = ["Block", "get_block", "NGNN", "SAGE", "SAGEPL", "SimpleGCN", "GCNConv", "Linear", "SAGEConv",
-           "add_node_noise", "segment_aggregate", "shuffle_pos", "topk_rewire", "flip_label", "noise_matrix",
+           "add_node_noise", "batch_norm_act", "segment_aggregate", "shuffle_pos", "topk_rewire", "flip_label", "noise_matrix",
            "EpochMeter", "split_accuracy", "metrics", "_lib"]

@@ -161,6 +161,14 @@ SIGNATURES = {
     # (added within ABI 22: symmetric-normalised GCN, the weighted aggregate)
     "ngnn_gcn_norm": (_int, [_p, _p, _p, _i64, _int, _p, _p, _p]),
     "ngnn_gcn_wagg": (_int, [_p, _i64, _i64, _p, _p, _p, _p, _p, _p, _i64, _p, _i64, _p]),
+    # (added within ABI 22: fused ReLU-BatchNorm-dropout)
+    "ngnn_bn_slab_rows": (_int, []),
+    "ngnn_bn_workspace_bytes": (_sz, [_i64, _i64]),
+    "ngnn_bn_fwd_train": (_int, [_p, _i64, _i64, _i64, _int, _p, _p, ctypes.c_double, ctypes.c_double, _p, _p,
+                                 _p, ctypes.c_float, ctypes.c_uint64, _p, _p, _i64, _p, _p, _p, _p, _sz, _p]),
+    "ngnn_bn_fwd_eval": (_int, [_p, _i64, _i64, _i64, _int, _p, _p, ctypes.c_double, _p, _p, _p, _i64, _p]),
+    "ngnn_bn_bwd": (_int, [_p, _i64, _p, _i64, _i64, _i64, _int, _p, _p, _p, _p, ctypes.c_float, ctypes.c_uint64,
+                           _p, _p, _p, _p, _i64, _p, _sz, _p]),
 }
 
 _lib = None

@@ -23,7 +23,7 @@ from .block import get_block
 from .infer import last_inference_plan  # noqa: F401  (per layer: "rowtile" / "narrow" / "loop")
 from .loader import IndexedRows
 from .nn import GCNConv, SAGEConv
-from .ops import add_node_noise
+from .ops import add_node_noise, batch_norm_act, batch_norm_act_supported
 
 
 def _refuse_sync_free(edge_index):
@@ -84,14 +84,24 @@ class SAGE(nn.Module):
             # receptive-field-bounded backward (ngnn/fused.py)
             return fused.sage_stack(self, x, block, *_dropout_seed(self, x, block))
         if self.use_bn:
-            x = self.bn1(x)
+            x = batch_norm_act(x, self.bn1)
+        seeds = None
         for i, conv in enumerate(self.convs):
             x = conv(x, block)
             if i != self.num_layers - 1:
-                x = x.relu()
                 if self.use_bn:
-                    x = self.bn2(x)
-                x = F.dropout(x, p=self.dropout, training=self.training)
+                    # ReLU, BatchNorm and dropout in one op (ngnn.ops.batch_norm_act:
+                    # HIP kernels when eager fp32, torch's ops otherwise); one
+                    # hash-dropout seed per call, stepped per layer as the fused
+                    # stack's, and drawn only when the kernels will use it
+                    if seeds is None:
+                        seeds = _dropout_seed(self, x, block) \
+                            if batch_norm_act_supported(x, self.bn2, self.training) else (0, None)
+                    x = batch_norm_act(x, self.bn2, relu=True, p=self.dropout, seed=seeds[0] + 7919 * i,
+                                       seed_dev=seeds[1])
+                else:
+                    x = x.relu()
+                    x = F.dropout(x, p=self.dropout, training=self.training)
         return x
 
     @torch.no_grad()
@@ -213,13 +223,14 @@ class SAGEPL(nn.Module):
 
     def _stack(self, x, block):
         if self.use_bn:
-            x = self.bn1(x)
+            x = batch_norm_act(x, self.bn1)
         for i, conv in enumerate(self.convs):
             x = conv(x, block)
             if i != self.num_layers - 1:
-                x = x.relu()
-                if self.use_bn:
-                    x = self.bn2(x)
+                if self.use_bn:  # ReLU and BatchNorm in one op; h needs the value before dropout
+                    x = batch_norm_act(x, self.bn2, relu=True)
+                else:
+                    x = x.relu()
                 h = x
                 x = F.dropout(x, p=self.dropout, training=self.training)
         return h, torch.log_softmax(x, dim=1), x

@@ -504,3 +504,120 @@ def shuffle_pos(features: torch.Tensor, device=None, prob: float = 0.1, seed: in
                                            _lib.ptr(out), F, _lib.stream_handle(x.device))
     _lib.check(rc, "ngnn_shuffle_rows")
     return out
+
+
+# ---- fused ReLU - BatchNorm1d - dropout (ngnn_bn_fwd_train / _fwd_eval / _bwd) ----
+
+class _BatchNormAct(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, bn, relu: bool, p: float, training: bool, seed: int, seed_dev):
+        xs, ldx = rows_ld(x)
+        n_rows, F = xs.shape
+        out = torch.empty(n_rows, F, dtype=xs.dtype, device=xs.device)
+        lib, st = _lib.load(), _lib.stream_handle(xs.device)
+        if not training:
+            with _timing.span("bn_fwd_eval", 2 * n_rows * F * 4):
+                rc = lib.ngnn_bn_fwd_eval(_lib.ptr(xs), ldx, n_rows, F, int(relu), _lib.ptr(weight), _lib.ptr(bias),
+                                          bn.eps, _lib.ptr(bn.running_mean), _lib.ptr(bn.running_var),
+                                          _lib.ptr(out), F, st)
+            _lib.check(rc, "ngnn_bn_fwd_eval")
+            return out
+        # rows: the batch mean, its fp32 rounding residual, invstd
+        stats = torch.empty(3, F, dtype=torch.float32, device=xs.device)
+        ws_bytes = lib.ngnn_bn_workspace_bytes(n_rows, F)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=xs.device)
+        momentum = -1.0 if bn.momentum is None else float(bn.momentum)
+        # algorithmic bytes: x twice (statistics, apply) + out
+        with _timing.span("bn_fwd_train", 3 * n_rows * F * 4):
+            rc = lib.ngnn_bn_fwd_train(_lib.ptr(xs), ldx, n_rows, F, int(relu), _lib.ptr(weight), _lib.ptr(bias),
+                                       bn.eps, momentum, _lib.ptr(bn.running_mean), _lib.ptr(bn.running_var),
+                                       _lib.ptr(bn.num_batches_tracked), p, seed, _lib.ptr(seed_dev),
+                                       _lib.ptr(out), F, _lib.ptr(stats[0]), _lib.ptr(stats[1]), _lib.ptr(stats[2]),
+                                       _lib.ptr(ws), ws_bytes, st)
+        _lib.check(rc, "ngnn_bn_fwd_train")
+        ctx.relu, ctx.p, ctx.seed, ctx.ldx = relu, p, seed, ldx
+        ctx.save_for_backward(xs, weight, stats, seed_dev)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        xs, weight, stats, seed_dev = ctx.saved_tensors
+        gs, ldg = rows_ld(g)
+        n_rows, F = xs.shape
+        dgamma, dbeta = torch.empty_like(stats[0]), torch.empty_like(stats[0])
+        # the input that needs no gradient (bn1 on batch.x): no dx pass at all
+        dx = torch.empty(n_rows, F, dtype=xs.dtype, device=xs.device) if ctx.needs_input_grad[0] else None
+        lib = _lib.load()
+        ws_bytes = lib.ngnn_bn_workspace_bytes(n_rows, F)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=xs.device)
+        # algorithmic bytes: dout and x for the sums, again (+ dx) for the dx pass
+        with _timing.span("bn_bwd", (2 if dx is None else 5) * n_rows * F * 4):
+            rc = lib.ngnn_bn_bwd(_lib.ptr(gs), ldg, _lib.ptr(xs), ctx.ldx, n_rows, F, int(ctx.relu),
+                                 _lib.ptr(weight), _lib.ptr(stats[0]), _lib.ptr(stats[1]), _lib.ptr(stats[2]),
+                                 ctx.p, ctx.seed,
+                                 _lib.ptr(seed_dev), _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(dx), F,
+                                 _lib.ptr(ws), ws_bytes, _lib.stream_handle(xs.device))
+        _lib.check(rc, "ngnn_bn_bwd")
+        return dx, dgamma, dbeta, None, None, None, None, None, None
+
+
+def batch_norm_act_supported(x: torch.Tensor, bn: torch.nn.BatchNorm1d, training: bool) -> bool:
+    """Whether ``batch_norm_act`` runs on the HIP kernels: a 2-D fp32 CUDA
+    ``x``, an affine ``bn`` with fp32 parameters that tracks its running
+    statistics, no stream capture in progress (a graph slot's padded rows
+    would enter the statistics), and, in eval mode, nothing to differentiate
+    (the kernels have no eval-mode backward)."""
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2):
+        return False
+    if bn.weight is None or bn.bias is None or bn.running_mean is None or bn.running_var is None \
+            or bn.num_batches_tracked is None:
+        return False
+    if any(t.dtype != torch.float32 or t.device != x.device
+           for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)):
+        return False
+    if x.size(1) != bn.num_features or torch.cuda.is_current_stream_capturing():
+        return False
+    if not training and torch.is_grad_enabled() and (x.requires_grad or bn.weight.requires_grad
+                                                     or bn.bias.requires_grad):
+        return False
+    return True
+
+
+def batch_norm_act(x: torch.Tensor, bn: torch.nn.BatchNorm1d, relu: bool = False, p: float = 0.0,
+                   training: bool | None = None, seed: int | None = None, seed_dev=None) -> torch.Tensor:
+    """``dropout(bn(relu(x)))`` -- the chain the reference runs per hidden
+    layer with ``use_bn`` (``sage.py:31-38``) -- on three launches forward and
+    three backward (``ngnn_bn_fwd_train`` / ``ngnn_bn_bwd``; one launch in eval
+    mode) instead of a torch launch per op and pass.  ``relu=False, p=0`` is
+    the plain ``bn(x)`` of the input features; an ``x`` that needs no gradient
+    skips the backward's dx pass.
+
+    ``bn`` holds the parameters and the buffers (state-dict keys unchanged);
+    its running statistics and ``num_batches_tracked`` move on the device as
+    ``nn.BatchNorm1d``'s.  ``training=None`` follows ``bn.training``.  The
+    dropout is the library's hash dropout keyed by ``(seed ^ *seed_dev, row,
+    column)`` (``seed=None``: drawn from torch's CPU generator), applied in
+    training only, like ``F.dropout(training=...)``.
+
+    Runs on the kernels when ``batch_norm_act_supported``; anything else
+    (bf16, a captured step, a ``bn`` without affine parameters or running
+    statistics, eval mode under autograd) is torch's ``relu`` /
+    ``nn.BatchNorm1d`` / ``F.dropout``, as before this op existed."""
+    training = bn.training if training is None else bool(training)
+    p = float(p)
+    if not batch_norm_act_supported(x, bn, training):
+        if training != bn.training:
+            raise ValueError("batch_norm_act: a training flag other than bn.training needs the HIP path")
+        y = bn(x.relu() if relu else x)
+        return torch.nn.functional.dropout(y, p=p, training=training)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"batch_norm_act: dropout probability has to be between 0 and 1, got {p}")
+    if training and x.size(0) < 2:  # nn.BatchNorm1d's own refusal
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(x.shape)}")
+    if not training or p == 0.0:
+        p, seed, seed_dev = 0.0, 0, None
+    elif seed is None:
+        seed = int(torch.randint(0, 1 << 62, (1,)).item())  # torch's (CPU) RNG stream
+    return _BatchNormAct.apply(x, bn.weight, bn.bias, bn, bool(relu), p, training,
+                               int(seed) & 0xFFFFFFFFFFFFFFFF, seed_dev)
