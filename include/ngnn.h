@@ -1396,6 +1396,52 @@ int ngnn_bn_bwd(const float *dout, int64_t ldg, const float *x, int64_t ldx, int
                 uint64_t seed, const uint64_t *seed_dev, float *dgamma, float *dbeta, float *dx, int64_t ldd,
                 void *ws, size_t ws_bytes, void *stream);
 
+/* ----------------------------------- hidden-state tap of the fused SAGE stack
+ * Added within ABI 22 (new entries only: nothing existing changed, so the
+ * version did not move).
+ *
+ * A stack that hands out h = relu(conv_{L-2}(...)) BEFORE dropout next to its
+ * logits (the reference's SAGEH and SAGEPL) runs that
+ * layer through ngnn_sage_fwd_raw with relu = 1, p_drop = 0 and applies the
+ * dropout with ngnn_dropout_rows; its backward folds the gradient that
+ * arrives at h into the layer's dz with ngnn_tap_grad.
+ *
+ * ngnn_dropout_rows: for rows r < min(n_rows, *n_rows_dev) (n_rows_dev
+ *   nullable) and columns c < F
+ *     out[r, c] = keep(r, c) ? h[r, c] * scale : +0.0
+ *   keep and scale are ngnn_device.h::Dropout's on (seed ^ *seed_dev, r, c)
+ *   (seed_dev nullable), r and c counted from the tensor's first row and
+ *   column: the mask and the one product of ngnn_sage_fwd_raw's epilogue, so
+ *   with h what that call stores for (relu = 1, p_drop = 0), out is bit for
+ *   bit what the same call stores for (relu = 1, p_drop, seed, seed_dev).
+ *   (One exception, never met by a computed activation: the row-tile
+ *   kernel's p_drop = 0.5 form takes ReLU as an integer max and so stores +0.0
+ *   where h is -0.0 or a negative-signed NaN; here such an h keeps its sign.)
+ *   p_drop = 0 copies, p_drop = 1 stores +0.0 everywhere.  out must not alias
+ *   h.  Rows at or past the bound and columns F .. ldo - 1 are not written.
+ * ngnn_tap_grad: for rows r < min(n_rows, *r_ptr) (r_ptr nullable)
+ *     dz = dy * [xd > 0] * yscale + dh * [h > 0]
+ *   The first term is ngnn_sage_wgrad's dz for y = xd (ReLU + dropout
+ *   backward), the second the ReLU backward of the gradient dh that reached
+ *   the tapped h.  xd == NULL (no dropout: xd would be h):
+ *   dz = (dy + dh) * [h > 0], yscale unused.  dy == NULL (nothing read xd):
+ *   dz = dh * [h > 0].  dz may alias dy.  Rows at or past the bound are left
+ *   untouched.
+ * One launch each, no allocation, no host synchronisation (capturable).  A
+ * lane group per row (16, 32 or 64 lanes by width); 16-B accesses when every
+ * base and leading dimension allows, 4-B otherwise.
+ * Before any launch: n_rows or F negative, p_drop outside [0, 1]:
+ * NGNN_E_ARG; a leading dimension (of a pointer that is read) < F:
+ * NGNN_E_SHAPE; n_rows or F > 2^31 - 1: NGNN_E_RANGE; n_rows == 0 or F == 0:
+ * success, no pointer read; then a NULL h / out (dh / h / dz), or out == h:
+ * NGNN_E_ARG. */
+int ngnn_dropout_rows(const float *h, int64_t ldh, int64_t n_rows, const int32_t *n_rows_dev, int64_t F,
+                      float p_drop, uint64_t seed, const uint64_t *seed_dev, float *out, int64_t ldo,
+                      void *stream);
+int ngnn_tap_grad(const float *dy, int64_t ldy, const float *xd, int64_t ldx, float yscale, const float *dh,
+                  int64_t ldg, const float *h, int64_t ldh, int64_t n_rows, const int32_t *r_ptr, int64_t F,
+                  float *dz, int64_t ldz, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

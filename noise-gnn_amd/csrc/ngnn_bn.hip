@@ -439,8 +439,6 @@ int check_common(int64_t n_rows, int64_t F) {
     return NGNN_OK;
 }
 
-bool bad_p(float p) { return !(p >= 0.0f && p <= 1.0f); }
-
 }  // namespace
 }  // namespace ngnn
 

@@ -33,6 +33,9 @@ inline bool aligned(const void *p, size_t a) {
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// a dropout probability outside [0, 1] (NaN included)
+inline bool bad_p(float p) { return !(p >= 0.0f && p <= 1.0f); }
+
 // Largest whole-buffer range in bytes: the kernels address a whole operand
 // through one buffer resource with unsigned 32-bit offsets, and offsets from
 // 0xF0000000 up mean "out of range" (kOOB) -- every such operand stays 4 KiB

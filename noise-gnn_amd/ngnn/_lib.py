@@ -169,6 +169,10 @@ SIGNATURES = {
     "ngnn_bn_fwd_eval": (_int, [_p, _i64, _i64, _i64, _int, _p, _p, ctypes.c_double, _p, _p, _p, _i64, _p]),
     "ngnn_bn_bwd": (_int, [_p, _i64, _p, _i64, _i64, _i64, _int, _p, _p, _p, _p, ctypes.c_float, ctypes.c_uint64,
                            _p, _p, _p, _p, _i64, _p, _sz, _p]),
+    # (added within ABI 22: the fused SAGE stack's hidden-state tap)
+    "ngnn_dropout_rows": (_int, [_p, _i64, _i64, _p, _i64, ctypes.c_float, ctypes.c_uint64, _p, _p, _i64, _p]),
+    "ngnn_tap_grad": (_int, [_p, _i64, _p, _i64, ctypes.c_float, _p, _i64, _p, _i64, _i64, _p, _i64, _p, _i64,
+                             _p]),
 }
 
 _lib = None

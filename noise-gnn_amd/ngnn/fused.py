@@ -941,6 +941,138 @@ def _layer_dgrad(lib, stream, block: Block, dy, ymask, yscale, wl, wr, red, dete
                          zero_tail)
 
 
+def _layers_backward(lib, stream, block: Block, reduce: str, p: float, L: int, acts, aggs, params, dy, grads,
+                     views, bp, pre_top: bool, rows_hint, need_dx: bool, deterministic: bool, tap=None):
+    """The per-layer backward of a stack from dy = d(acts[L]) down: each
+    layer's weight gradients into grads[3 i : 3 i + 3], then its input
+    gradient; returns d(acts[0]) when need_dx.  bp / pre_top / rows_hint:
+    _bwd_bounds'.  tap = (dh, h) (sage_stack_tap): the gradient dh that
+    reached h = relu(conv_{L-2}), the value acts[L - 1] is the dropout of (or
+    h itself, without dropout); one ngnn_tap_grad launch folds it into layer
+    L - 2's dz, which then needs no mask.  dy may be None with a tap."""
+    dev, N = block.rowptr.device, block.n_dst
+    red = _lib.REDUCE[reduce]
+    for i in reversed(range(L)):
+        h_in, y_out, agg = acts[i], acts[i + 1], aggs[i]
+        tapped = tap is not None and i == L - 2
+        if tapped:
+            dy = _tap_grad(lib, stream, dy, y_out, dropout_scale(p) if p > 0.0 else 1.0, *tap, bp[i + 1])
+        if dy is None:  # (a tapped stack whose logits nothing read: no output-layer term)
+            continue
+        if _debug_grads is not None:  # test/debug hook: d(acts[i+1]) per layer
+            _debug_grads.append((i, dy.detach().clone(),
+                                 None if agg is None else agg.detach().clone(),
+                                 h_in.detach().clone()))
+        wl, bl, wr = params[3 * i:3 * i + 3]
+        gcn = wr is None  # GCN layer: SAGE with W_r = 0 (no root-term gradient)
+        if gcn:
+            wr = _zeros_like_cached(wl)
+        hidden = i != L - 1
+        ymask = y_out if (hidden and not tapped) else None
+        yscale = dropout_scale(p) if (ymask is not None and p > 0.0) else 1.0
+        agg, dwl, dbl, dwr = _layer_wgrad(lib, stream, block, i, dy, ymask, yscale, h_in, agg, wl, bl,
+                                          wr, gcn, views[3 * i:3 * i + 3],
+                                          None if hidden else rows_hint, red, bp[i + 1])
+        grads[3 * i:3 * i + 3] = [dwl, dbl, None if gcn else dwr]
+        if i == 0 and not need_dx:
+            break
+        if not (pre_top and i == L - 1):
+            _lib.check(lib.ngnn_block_prefix_stats(_lib.ptr(block.rowptr), _lib.ptr(block.col),
+                                                   bp[i + 1], None, bp[i], block.E, stream),
+                       "ngnn_block_prefix_stats")
+        if ymask is not None and ymask.dtype == torch.bfloat16:
+            # the input-gradient kernels read an fp32 mask: widen its rows
+            # below the output-gradient bound (device-side)
+            Fo = wl.shape[0]
+            ym = _workspace(dev, "ymask_f32", N * Fo * 4).view(torch.float32)[:N * Fo].view(N, Fo)
+            _lib.check(lib.ngnn_widen_bf16_rows(_lib.ptr(ymask), ymask.stride(0), Fo, N,
+                                                bp[i + 1], _lib.ptr(ym), Fo, stream),
+                       "ngnn_widen_bf16_rows")
+            ymask = ym
+        dy = _layer_dgrad(lib, stream, block, dy, ymask, yscale, wl, wr, red, deterministic, h_in, agg,
+                          bp[i + 1], bp[i], int(i == 0))
+    return dy if (need_dx and L > 0) else None
+
+
+def _tap_grad(lib, stream, dy, xd, yscale: float, dh, h, r_ptr: int):
+    """dz = dy [xd > 0] yscale + dh [h > 0] on rows < *r_ptr, into dy's rows
+    (a new buffer without dy); xd is h: no dropout ran, no mask of its own."""
+    N, F = h.shape
+    dz = dy if dy is not None else torch.empty(N, F, dtype=torch.float32, device=h.device)
+    xd = None if (xd is h or xd.data_ptr() == h.data_ptr()) else xd
+    with _timing.span("sage_tap_grad", (5 if xd is not None else 4) * N * F * 4):
+        rc = lib.ngnn_tap_grad(_lib.ptr(dy), dy.stride(0) if dy is not None else F, _lib.ptr(xd),
+                               xd.stride(0) if xd is not None else F, yscale, _lib.ptr(dh), dh.stride(0),
+                               _lib.ptr(h), h.stride(0), N, r_ptr, F, _lib.ptr(dz), dz.stride(0), stream)
+    _lib.check(rc, "ngnn_tap_grad")
+    return dz
+
+
+def _layers_forward(x, block: Block, reduce: str, p_drop: float, seed: int, seed_dev, w_bf16: bool, params,
+                    acts, aggs, tap: bool = False):
+    """The per-layer forward of a stack: layer i's output appended to acts, its
+    saved aggregate (None: rebuilt by the backward) to aggs; returns (logits,
+    h_tap).  tap (sage_stack_tap): layer L - 2 runs without dropout -- h_tap,
+    the hidden state before dropout -- and ngnn_dropout_rows then makes what
+    the output layer reads (and acts holds) with that layer's seed."""
+    L = len(params) // 3
+    h, h_tap = x, None
+    for i in range(L):
+        wl, bl, wr = params[3 * i:3 * i + 3]
+        last = i == L - 1
+        tapped = tap and i == L - 2
+        relu, p_i, seed_i = not last, (0.0 if (last or tapped) else p_drop), seed + 7919 * i
+        x_dev = block.x_dev if i == 0 else None
+        xrow = dict(xrow_dev=block.xrow_dev, x_rows=block.x_rows) if i == 0 else {}
+        pk = block.wl_prepacked
+        if (pk is not None and i == 0 and wr is not None and (len(pk) < 3 or pk[2].armed)
+                and pk[0].data_ptr() == wl.data_ptr() and pk[0].shape == wl.shape):
+            xrow["wl_packed"] = pk[1]
+            if len(pk) > 2:
+                pk[2].armed = False  # one forward per load (graphs.PackState)
+        if wr is None and h.size(1) > wl.shape[0]:
+            # GCN layer narrowing its input: transform first (PyG's order),
+            # no saved aggregate (rebuilt for the rows backward needs)
+            agg = None
+            h = gcn_transform_first(h, block, wl, bl, relu, p_i, seed_i, seed_dev, x_dev,
+                                    span=f"gcn_fwd_l{i}", **xrow)
+        else:
+            # the output layer aggregates in the F_out-wide space when it can
+            # (its K-wide aggregate is rebuilt for the seed rows in backward)
+            narrow = (wr is not None and last and i > 0
+                      and narrow_ok(reduce, h.size(1), wl.shape[0], False, 0.0))
+            agg = None if narrow else agg_buffer(h.size(0), h.size(1), h.device, wl.shape[0])
+            # a bf16 model's hidden activations are bf16 rows (as the
+            # reference's bf16 layers produce them): half the bytes written
+            # here and read by the next layer and the backward.  (MAX keeps
+            # fp32: its backward tie test reads the layer input; GCN stacks
+            # keep fp32 too: their transform-first layers read fp32 rows.)
+            h = sage_layer_fwd(h, block, reduce, wl, bl, wr, relu=relu, p_drop=p_i,
+                               seed=seed_i, agg_out=agg, seed_dev=seed_dev, x_dev=x_dev,
+                               span=f"sage_fwd_l{i}", narrow=narrow, w_bf16=w_bf16,
+                               out_bf16=(w_bf16 and not last and reduce != "max"
+                                         and wr is not None), **xrow)
+        if tapped:
+            h_tap = h
+            if p_drop > 0.0:
+                h = _dropout_rows(h, block, p_drop, seed_i, seed_dev)
+        acts.append(h)
+        aggs.append(agg)
+    return h, h_tap
+
+
+def _dropout_rows(h, block: Block, p_drop: float, seed: int, seed_dev):
+    """dropout(h) as the layer's own epilogue would have stored it (ngnn_dropout_rows)."""
+    N, F = h.shape
+    out = torch.empty(N, F, dtype=torch.float32, device=h.device)
+    with _timing.span("sage_tap_dropout", 2 * N * F * 4):
+        rc = _lib.load().ngnn_dropout_rows(_lib.ptr(h), h.stride(0), N, _lib.ptr(block.n_rows_dev), F,
+                                           float(p_drop), seed & (2**64 - 1), _lib.ptr(seed_dev), _lib.ptr(out),
+                                           out.stride(0), _lib.stream_handle(h.device))
+    _lib.check(rc, "ngnn_dropout_rows")
+    return out
+
+
 class _SAGEStack(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, block: Block, reduce: str, p_drop: float, seed: int, seed_dev, gouts,
@@ -960,42 +1092,8 @@ class _SAGEStack(torch.autograd.Function):
             acts += [h1, h]
             aggs += [agg0, None]
             L = 0  # (the per-layer loop below is skipped)
-        for i in range(L):
-            wl, bl, wr = params[3 * i:3 * i + 3]
-            last = i == L - 1
-            relu, p_i, seed_i = not last, (0.0 if last else p_drop), seed + 7919 * i
-            x_dev = block.x_dev if i == 0 else None
-            xrow = dict(xrow_dev=block.xrow_dev, x_rows=block.x_rows) if i == 0 else {}
-            pk = block.wl_prepacked
-            if (pk is not None and i == 0 and wr is not None and (len(pk) < 3 or pk[2].armed)
-                    and pk[0].data_ptr() == wl.data_ptr() and pk[0].shape == wl.shape):
-                xrow["wl_packed"] = pk[1]
-                if len(pk) > 2:
-                    pk[2].armed = False  # one forward per load (graphs.PackState)
-            if wr is None and h.size(1) > wl.shape[0]:
-                # GCN layer narrowing its input: transform first (PyG's order),
-                # no saved aggregate (rebuilt for the rows backward needs)
-                agg = None
-                h = gcn_transform_first(h, block, wl, bl, relu, p_i, seed_i, seed_dev, x_dev,
-                                        span=f"gcn_fwd_l{i}", **xrow)
-            else:
-                # the output layer aggregates in the F_out-wide space when it can
-                # (its K-wide aggregate is rebuilt for the seed rows in backward)
-                narrow = (wr is not None and last and i > 0
-                          and narrow_ok(reduce, h.size(1), wl.shape[0], False, 0.0))
-                agg = None if narrow else agg_buffer(h.size(0), h.size(1), h.device, wl.shape[0])
-                # a bf16 model's hidden activations are bf16 rows (as the
-                # reference's bf16 layers produce them): half the bytes written
-                # here and read by the next layer and the backward.  (MAX keeps
-                # fp32: its backward tie test reads the layer input; GCN stacks
-                # keep fp32 too: their transform-first layers read fp32 rows.)
-                h = sage_layer_fwd(h, block, reduce, wl, bl, wr, relu=relu, p_drop=p_i,
-                                   seed=seed_i, agg_out=agg, seed_dev=seed_dev, x_dev=x_dev,
-                                   span=f"sage_fwd_l{i}", narrow=narrow, w_bf16=w_bf16,
-                                   out_bf16=(w_bf16 and not last and reduce != "max"
-                                             and wr is not None), **xrow)
-            acts.append(h)
-            aggs.append(agg)
+        if L:
+            h, _ = _layers_forward(x, block, reduce, p_drop, seed, seed_dev, w_bf16, params, acts, aggs)
         if _debug_acts is not None:
             _debug_acts.append([a.detach().float().clone() for a in acts[1:-1]])
         ctx.block, ctx.reduce, ctx.p_drop, ctx.L = block, reduce, p_drop, len(params) // 3
@@ -1056,42 +1154,8 @@ class _SAGEStack(torch.autograd.Function):
         if rows_hint is None:
             _lib.check(lib.ngnn_row_extent(_lib.ptr(dy), dy.stride(0), N, dy.size(1), bp[L],
                                            stream), "ngnn_row_extent")
-        red = _lib.REDUCE[reduce]
-        for i in reversed(range(L)):
-            h_in, y_out, agg = acts[i], acts[i + 1], aggs[i]
-            if _debug_grads is not None:  # test/debug hook: d(acts[i+1]) per layer
-                _debug_grads.append((i, dy.detach().clone(),
-                                     None if agg is None else agg.detach().clone(),
-                                     h_in.detach().clone()))
-            wl, bl, wr = params[3 * i:3 * i + 3]
-            gcn = wr is None  # GCN layer: SAGE with W_r = 0 (no root-term gradient)
-            if gcn:
-                wr = _zeros_like_cached(wl)
-            hidden = i != L - 1
-            ymask = y_out if hidden else None
-            yscale = dropout_scale(p) if (hidden and p > 0.0) else 1.0
-            agg, dwl, dbl, dwr = _layer_wgrad(lib, stream, block, i, dy, ymask, yscale, h_in, agg, wl, bl,
-                                              wr, gcn, views[3 * i:3 * i + 3],
-                                              None if hidden else rows_hint, red, bp[i + 1])
-            grads[3 * i:3 * i + 3] = [dwl, dbl, None if gcn else dwr]
-            if i == 0 and not need_dx:
-                break
-            if not (pre_top and i == L - 1):
-                _lib.check(lib.ngnn_block_prefix_stats(_lib.ptr(block.rowptr), _lib.ptr(block.col),
-                                                       bp[i + 1], None, bp[i], block.E, stream),
-                           "ngnn_block_prefix_stats")
-            if ymask is not None and ymask.dtype == torch.bfloat16:
-                # the input-gradient kernels read an fp32 mask: widen its rows
-                # below the output-gradient bound (device-side)
-                Fo = wl.shape[0]
-                ym = _workspace(dev, "ymask_f32", N * Fo * 4).view(torch.float32)[:N * Fo].view(N, Fo)
-                _lib.check(lib.ngnn_widen_bf16_rows(_lib.ptr(ymask), ymask.stride(0), Fo, N,
-                                                    bp[i + 1], _lib.ptr(ym), Fo, stream),
-                           "ngnn_widen_bf16_rows")
-                ymask = ym
-            dy = _layer_dgrad(lib, stream, block, dy, ymask, yscale, wl, wr, red, deterministic, h_in, agg,
-                              bp[i + 1], bp[i], int(i == 0))
-        dx = dy if (need_dx and L > 0) else None
+        dx = _layers_backward(lib, stream, block, reduce, p, L, acts, aggs, params, dy, grads, views, bp,
+                              pre_top, rows_hint, need_dx, deterministic)
         return (dx, None, None, None, None, None, None, None, None, *grads)
 
 
@@ -1320,6 +1384,129 @@ def sage_stack(model, x, block: Block, seed: int, seed_dev=None) -> torch.Tensor
         params += [conv.lin_l.weight, conv.lin_l.bias, conv.lin_r.weight]
     aggr = "sum" if model.convs[0].aggr == "add" else model.convs[0].aggr
     return _run_stack(model, x, block, seed, seed_dev, params, aggr, keep_bf16_x=True)
+
+
+def _tap_bounds(block: Block, L: int, dy, rows_hint, dh, h_hint):
+    """_bwd_bounds for a tapped stack whose h received the gradient dh: (bnd,
+    bp, rows_hint).  bp[L - 1] -- the rows of d(xd) and of layer L - 2's dz --
+    must also cover the rows of dh that can be nonzero: its word starts at
+    their extent (h_hint, the loss's _ngnn_nonzero_rows, else ngnn_row_extent
+    on the device; rows_hint: the same for dy) and
+    ngnn_block_prefix_stats takes the max with what it finds there; every
+    input-gradient route writes every row below that bound (include/ngnn.h),
+    so ngnn_tap_grad reads no unwritten row of d(xd).  dy None (nothing read
+    the logits): bp[L - 1] is dh's extent alone."""
+    dev, N = dh.device, block.n_dst
+    R = int(rows_hint) if rows_hint is not None else 0
+    Rh = max(R, min(int(h_hint), N)) if h_hint is not None else R
+    key = (dev, "bnd_tap", L, R, Rh)
+    base = _ws.get(key)
+    if base is None:
+        base = torch.full((L + 1,), R, dtype=torch.int32, device=dev)
+        base[L - 1] = Rh
+        _ws[key] = base
+    bnd = torch.empty(L + 1, dtype=torch.int32, device=dev)
+    bnd.copy_(base)
+    bp = [bnd.data_ptr() + 4 * j for j in range(L + 1)]
+    lib, stream = _lib.load(), _lib.stream_handle(dev)
+    for g, hint, word in ((dy, rows_hint, bp[L]), (dh, h_hint, bp[L - 1])):
+        if g is not None and hint is None:
+            _lib.check(lib.ngnn_row_extent(_lib.ptr(g), g.stride(0), N, g.size(1), word, stream),
+                       "ngnn_row_extent")
+    return bnd, bp
+
+
+def _rows_view(g):
+    """g as rows the kernels can read: unit column stride, rows apart."""
+    return g if (g.stride(1) == 1 and g.stride(0) >= g.size(1)) else g.contiguous()
+
+
+class _SAGEStackTap(torch.autograd.Function):
+    """The SAGE stack with a hidden-state tap: (logits, h), h = relu(conv_{L-2})
+    before dropout.  Per-layer kernels only; layer L - 2 runs without dropout
+    and ngnn_dropout_rows makes the output layer's input.  Backward: without a
+    gradient into h, _SAGEStack's per-layer backward launch for launch; with
+    one, a row-extent launch for its bound and one ngnn_tap_grad launch."""
+
+    @staticmethod
+    def forward(ctx, x, block: Block, reduce: str, p_drop: float, seed: int, seed_dev, *params):
+        acts, aggs = [x], []
+        out, h = _layers_forward(x, block, reduce, p_drop, seed, seed_dev, False, params, acts, aggs, tap=True)
+        if _debug_acts is not None:
+            _debug_acts.append([a.detach().float().clone() for a in acts[1:-1]])
+        ctx.block, ctx.reduce, ctx.p_drop, ctx.L = block, reduce, p_drop, len(params) // 3
+        ctx.h_partial = False
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(*acts, *aggs, *params, h)
+        return out, h
+
+    @staticmethod
+    def backward(ctx, dout, dh):
+        block, reduce, p, L = ctx.block, ctx.reduce, ctx.p_drop, ctx.L
+        saved = ctx.saved_tensors
+        acts, aggs, params, h = saved[:L + 1], saved[L + 1:2 * L + 1], saved[2 * L + 1:-1], saved[-1]
+        grads = [None] * (3 * L)
+        none5 = (None,) * 5
+        if dout is None and dh is None:
+            return (None, *none5, *grads)
+        lib = _lib.load()
+        stream = _lib.stream_handle(h.device)
+        need_dx = ctx.needs_input_grad[0]
+        deterministic = torch.are_deterministic_algorithms_enabled()
+        dy = _rows_view(dout) if dout is not None else None
+        # (bnd stays referenced until the last launch is enqueued: see _SAGEStack.backward)
+        if dh is None:
+            bnd, bp, pre_top, rows_hint = _bwd_bounds(ctx, dout, L, need_dx)
+            if rows_hint is None:
+                _lib.check(lib.ngnn_row_extent(_lib.ptr(dy), dy.stride(0), block.n_dst, dy.size(1), bp[L],
+                                               stream), "ngnn_row_extent")
+            tap = None
+        else:
+            rows_hint = getattr(dout, "_ngnn_nonzero_rows", None)  # set by ngnn.losses
+            h_hint = getattr(dh, "_ngnn_nonzero_rows", None)
+            dh = _rows_view(dh)
+            bnd, bp = _tap_bounds(block, L, dy, rows_hint, dh, h_hint)
+            pre_top, tap = False, (dh, h)
+        dx = _layers_backward(lib, stream, block, reduce, p, L, acts, aggs, params, dy, grads, [None] * (3 * L),
+                              bp, pre_top, rows_hint, need_dx, deterministic, tap=tap)
+        del bnd
+        return (dx, *none5, *grads)
+
+
+def _graph_slot_block(block: Block) -> bool:
+    return (block.x_dev is not None or block.xrow_dev is not None or block.n_rows_dev is not None
+            or block.n_edge_rows_dev is not None or block.r_next is not None or block.loss_head is not None
+            or block.wl_prepacked is not None)
+
+
+def sage_tap_supported(model, x) -> bool:
+    """sage_stack_tap's envelope: sage_stack_supported restricted to fp32 rows
+    and parameters and at least two layers."""
+    return (sage_stack_supported(model, x) and x.dtype == torch.float32 and len(model.convs) >= 2
+            and all(q.dtype == torch.float32 for conv in model.convs
+                    for q in (conv.lin_l.weight, conv.lin_l.bias, conv.lin_r.weight)))
+
+
+def sage_stack_tap(model, x, block: Block, seed: int, seed_dev=None, training: bool = True):
+    """(logits, h) of a SAGE stack, h the last hidden activation after ReLU and
+    before dropout (what the reference's SAGEH and SAGEPL return), as ONE
+    autograd node with two outputs on the per-layer kernels.  `training`
+    (not model.training) decides the dropout, as SAGEH.forward's argument.
+    Eager blocks only: a graph slot's block (device-side counts, a zero-copy
+    input, a loss head) raises."""
+    if _graph_slot_block(block):
+        raise _lib.NGNNError("sage_stack_tap runs eager blocks only: this block carries a graph slot's "
+                             "device-side fields (capturing the tapped stack is not supported)")
+    if not sage_tap_supported(model, x):
+        raise _lib.NGNNError("sage_stack_tap: fp32 rows and parameters, one aggregation, no batch norm, "
+                             "num_layers >= 2 (check sage_tap_supported first)")
+    params = []
+    for conv in model.convs:
+        params += [conv.lin_l.weight, conv.lin_l.bias, conv.lin_r.weight]
+    aggr = "sum" if model.convs[0].aggr == "add" else model.convs[0].aggr
+    p = float(model.dropout) if training else 0.0
+    xc = x if (x.stride(1) == 1 and x.stride(0) >= x.size(1)) else x.contiguous()
+    return _SAGEStackTap.apply(xc, block, aggr, p, int(seed), seed_dev, *params)
 
 
 class _GradViews:

@@ -1,8 +1,9 @@
-"""Drop-in model wrappers: ``SAGE``, ``SAGEPL``, ``SimpleGCN`` and the ``NGNN`` factory.
+"""Drop-in model wrappers: ``SAGE``, ``SAGEH``, ``SAGEPL``, ``SimpleGCN`` and the ``NGNN`` factory.
 
 Mirror the reference classes one to one:
 
 * ``SAGE``      src/models/layers/sage.py:6-79
+* ``SAGEH``     src/models/layers/sageH.py:6-35
 * ``SAGEPL``    src/models/layers/sagePL.py:6-94
 * ``SimpleGCN`` src/models/layers/convolution.py:7-53
 * ``NGNN``      src/models/model.py:10-69 (module string -> network, Adam optimiser)
@@ -35,10 +36,11 @@ def _refuse_sync_free(edge_index):
                          "use NeighborLoader(sync_free=False) for eager training")
 
 
-def _dropout_seed(model, x, block):
-    """(host seed, device seed word) of a fused stack's hash dropout."""
+def _dropout_seed(model, x, block, training=None):
+    """(host seed, device seed word) of a fused stack's hash dropout;
+    training: what decides the dropout (default: model.training)."""
     seed, seed_dev = 0, None
-    if model.training and model.dropout > 0:
+    if (model.training if training is None else training) and model.dropout > 0:
         if torch.cuda.is_current_stream_capturing():
             # HIP-graph capture: a device seed, fresh at every replay -- the
             # slot's (advanced by each slot load), else drawn by torch's
@@ -165,6 +167,64 @@ class SimpleGCN(nn.Module):
         return _inference(self.convs, self.num_layers, x_all, subgraph_loader, device)
 
 
+def _tapped_composition(convs, x, block, dropout, training):
+    """(logits, h) layer by layer on the per-conv path: relu and F.dropout as
+    torch ops, h the last hidden activation before dropout."""
+    h = None
+    for i, conv in enumerate(convs):
+        x = conv(x, block)
+        if i != len(convs) - 1:
+            h = x.relu()
+            x = F.dropout(h, p=dropout, training=training)
+    return x, h
+
+
+class SAGEH(nn.Module):
+    """The reference's ``SAGEH`` (src/models/layers/sageH.py:6-35, what
+    ``module: 'sageH'`` selects): a GraphSAGE stack whose forward returns
+    ``(logits, h_out)``, ``h_out`` the last hidden activation after ReLU and
+    before dropout.  One autograd node with two outputs on the fused
+    per-layer kernels (``fused.sage_stack_tap``); inputs outside its envelope
+    (non-fp32) take the per-conv composition.
+
+    ``act`` and ``bnl`` are the reference's unused members (sageH.py:14,21),
+    kept so that its checkpoints load with ``strict=True``.  Dropout follows
+    the ``training`` ARGUMENT of forward, not ``self.training``
+    (sageH.py:27,34).  ``num_layers >= 2``: with one layer the reference's
+    ``h_out`` is never assigned and its forward raises; here the constructor
+    does.  No ``inference`` method, as the reference has none.
+    """
+
+    def __init__(self, in_size, hidden_size, out_size, num_layers, dropout=0.5, aggr: str = "mean"):
+        super().__init__()
+        if num_layers < 2:
+            raise ValueError("SAGEH needs num_layers >= 2: the hidden state it returns is the last "
+                             "hidden layer's (undefined in the reference for one layer)")
+        self.num_layers = num_layers
+        self.dropout = dropout
+        self.act = nn.PReLU()
+        self.convs = nn.ModuleList()
+        self.convs.append(SAGEConv(in_size, hidden_size, aggr=aggr))
+        for _ in range(num_layers - 2):
+            self.convs.append(SAGEConv(hidden_size, hidden_size, aggr=aggr))
+        self.convs.append(SAGEConv(hidden_size, out_size, aggr=aggr))
+        self.bnl = nn.BatchNorm1d(128)
+
+    def reset_parameters(self):
+        for conv in self.convs:  # (the convs only, as the reference: sageH.py:23-25)
+            conv.reset_parameters()
+
+    def forward(self, x, edge_index, training=True):
+        _refuse_sync_free(edge_index)
+        if isinstance(x, IndexedRows):  # eager: gather the rows
+            x = x.materialize()
+        block = get_block(edge_index, x.size(0))
+        if fused.sage_tap_supported(self, x):
+            seed, seed_dev = _dropout_seed(self, x, block, training=training)
+            return fused.sage_stack_tap(self, x, block, seed, seed_dev, training=training)
+        return _tapped_composition(self.convs, x, block, self.dropout, training)
+
+
 class SAGEPL(nn.Module):
     """The reference's ``SAGEPL`` (src/models/layers/sagePL.py:6-94, what
     ``module: 'sagePL'`` selects): a GraphSAGE stack with a learnable noise
@@ -179,14 +239,20 @@ class SAGEPL(nn.Module):
     layer 0 hands back the input gradient that trains the table.  State-dict
     keys are the reference's (``noise``, ``convs.{i}.lin_l.weight`` ...).
 
+    ``fused_stack=True`` (opt-in) runs each pass as one autograd node on the
+    fused per-layer kernels instead (``fused.sage_stack_tap``: ReLU and
+    dropout in the layer epilogue, the receptive-field-bounded backward);
+    ``use_bn=True`` and non-fp32 inputs keep the per-conv path.
+
     ``num_layers >= 2``: with one layer the reference's ``h`` is never
     assigned (sagePL.py:60 runs for hidden layers only) and its forward
     raises; here the constructor does.  The noise path is fp32 only.
     """
 
     def __init__(self, in_size, hidden_size, out_size, num_layers, nbr_nodes, dropout=0.5,
-                 use_bn=False, aggr: str = "mean"):
+                 use_bn=False, aggr: str = "mean", fused_stack: bool = False):
         super().__init__()
+        self.fused_stack = bool(fused_stack)
         if num_layers < 2:
             raise ValueError("SAGEPL needs num_layers >= 2: the hidden state it returns is the last "
                              "hidden layer's (undefined in the reference for one layer)")
@@ -222,6 +288,9 @@ class SAGEPL(nn.Module):
         return add_node_noise(x, self.noise, n_id=n_id, rate=noise_rate, sign=n_id is None)
 
     def _stack(self, x, block):
+        if self.fused_stack and fused.sage_tap_supported(self, x):  # (excludes use_bn)
+            z, h = fused.sage_stack_tap(self, x, block, *_dropout_seed(self, x, block), training=self.training)
+            return h, torch.log_softmax(z, dim=1), z
         if self.use_bn:
             x = batch_norm_act(x, self.bn1)
         for i, conv in enumerate(self.convs):
@@ -285,7 +354,7 @@ class NGNN(object):
 
     def __init__(self, in_size=100, hidden_size=128, out_size=47, num_layers=2, dropout=0.5,
                  lr=0.001, optimizer='adam', module='sage', nbr_nodes=1, use_bn=False, wd=0.0005,
-                 aggr='mean', gcn_normalize=False):
+                 aggr='mean', sagepl_fused=False, gcn_normalize=False):
         self.criterion = None
         self.score_func = None
         self.metric_name = None
@@ -297,6 +366,7 @@ class NGNN(object):
         self.use_bn = use_bn
         self.aggr = aggr
         self.gcn_normalize = gcn_normalize
+        self.sagepl_fused = sagepl_fused
         self.init_network()
         self.init_optimizer()
 
@@ -312,10 +382,15 @@ class NGNN(object):
         elif self.module == 'sagePL':  # model.py:57-63 (use_bn is not passed on there)
             self.network = SAGEPL(in_size=self.in_size, hidden_size=self.hidden_size,
                                   out_size=self.out_size, num_layers=self.num_layers,
-                                  dropout=self.dropout, nbr_nodes=self.nbr_nodes, aggr=self.aggr)
+                                  dropout=self.dropout, nbr_nodes=self.nbr_nodes, aggr=self.aggr,
+                                  fused_stack=self.sagepl_fused)
+        elif self.module == 'sageH':  # model.py:51-56
+            self.network = SAGEH(in_size=self.in_size, hidden_size=self.hidden_size,
+                                 out_size=self.out_size, num_layers=self.num_layers,
+                                 dropout=self.dropout, aggr=self.aggr)
         else:
             raise ValueError(f"module {self.module!r} is outside this path "
-                             "(supported: 'sage', 'sagePL', 'gcn'; see DESIGN.md scope)")
+                             "(supported: 'sage', 'sageH', 'sagePL', 'gcn'; see DESIGN.md scope)")
 
     def init_optimizer(self):
         if self.optimizer == 'adam':
